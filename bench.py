@@ -8,8 +8,14 @@ GAE + whole-batch advantage normalisation (HIP), then 10 epochs x 8 minibatches 
 N*T/8 with clip_grad_norm_(0.5) + Adam (PyTorch-ROCm fp32, the reference's precision).
 ppo_train.py defaults otherwise (lr 3e-4, gamma .99, lam .95, clip .2, vf .5, ent .05).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K iterations and prints the line (value, ms_per_step, the phases and
+the per-kernel table / rooflines read from the HIP events of the timed iterations themselves).  --full adds what
+takes runs of its own after the timed region: the fc1 GEMMs timed alone, the tiers (env only, 2M envs, floors,
+hard 22x22, FOMAML) and the CPU baseline.  --dump-outputs DIR writes what the last timed iteration computed
+(DIR/<name>.npy, float32 / float64): seeds and arguments fix every input, so two builds compare output for output.
 
 Rank r owns envs [r*N, (r+1)*N) seeded 777 + global index (weak scaling); the update
 all-reduces the f32 gradient once per optimizer step and the advantage moments once
@@ -76,8 +82,13 @@ def parse():
     ap.add_argument("--timer-every", type=int, default=4,
                     help="HIP-event timing of every k-th launch of each kernel in the timed region (kernels table, "
                          "rooflines); the event records cost the loop ~2-3 %% when every launch is timed")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-tiers", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run what needs runs of its own: fc1's GEMMs alone "
+                         "(roofline_x6_standalone), the tiers and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-tiers", action="store_true", help="with --full: leave the tiers out")
     ap.add_argument("--env-tier-only", action="store_true",
                     help="only the HBM-scale env tier (2M envs; for the k_env_step rocprofv3 --pmc pass)")
     ap.add_argument("--no-dedup", action="store_true",
@@ -89,6 +100,34 @@ def parse():
                     help="cfg 5 instead: FOMAML meta-iterations, tasks_per_batch=32 x k_steps=256")
     ap.add_argument("--tasks", type=int, default=32)
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 60 << 20  # a dump holds at most 64 MB
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: tensor / array / list} -> DIR/<name>.npy as float32 (float64 kept).  Each array has an
+    equal share of DUMP_BUDGET_BYTES; a larger one is written as a fixed sample of its flattened elements (sorted
+    indices drawn by numpy's RandomState(0): the same elements in every run of the same shapes)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            keep = np.sort(np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def ppo_outputs(agent, last_value, stats):
+    """What one timed iteration hands its caller: collect_rollouts()'s bootstrap values and the rollout it stored
+    ([T][N] fields of the code buffer), update()'s statistics, advantages / returns and the parameters it stepped."""
+    buf = agent.buf
+    return {"last_value": last_value, "update_stats": [stats[k] for k in sorted(stats)],
+            "actions": buf.actions, "logprobs": buf.logprobs, "values": buf.values, "rewards": buf.rewards,
+            "dones": buf.dones, "advantages": agent.last_adv_normalized, "returns": buf.returns,
+            "parameters": np.concatenate([p.detach().cpu().numpy().reshape(-1) for p in agent.ac.parameters()])}
 
 
 def fomaml_bench(args):
@@ -108,10 +147,17 @@ def fomaml_bench(args):
         fm.meta_train_step(seeds(), k_support=args.k_steps, k_query=args.k_steps)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    res = None
     for _ in range(args.steps):
-        fm.meta_train_step(seeds(), k_support=args.k_steps, k_query=args.k_steps)
+        res = fm.meta_train_step(seeds(), k_support=args.k_steps, k_query=args.k_steps)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if args.dump_outputs and res is not None:
+        # the meta step's return (loss, episode return / length, the last task's statistics) and the meta policy
+        dump_outputs(args.dump_outputs, {
+            "meta_step": list(res[:3]) + [res[3][k] for k in sorted(res[3])],
+            "parameters": np.concatenate([p.detach().cpu().numpy().reshape(-1)
+                                          for p in fm.meta_policy.parameters()])})
     steps = args.steps * args.tasks * 2 * args.k_steps
     print(json.dumps({"metric": "FOMAML env-steps/sec (support+query rollouts, inner SGD, meta Adam)",
                       "value": round(steps / el, 1), "unit": "env-steps/s", "n_gpus": 1, "steps": args.steps,
@@ -620,13 +666,14 @@ def main():
     state["phase"] = "timed"
     nat.KernelTimer.start(every=args.timer_every)
     ph = []
+    lv = stats = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
         e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
         e0.record()
         lv = agent.collect_rollouts()
         e1.record()
-        agent.update(lv)
+        stats = agent.update(lv)
         e2.record()
         ph.append((e0, e1, e2))
     torch.cuda.synchronize()
@@ -665,6 +712,9 @@ def main():
         if rank != 0:
             dist.destroy_process_group()
             return
+    if args.dump_outputs and stats is not None:  # rank 0's share of a multi-rank run
+        state["phase"] = "dump"
+        dump_outputs(args.dump_outputs, ppo_outputs(agent, lv, stats))
     dominant = max(kernels, key=lambda k: kernels[k]["total_ms"])
     fc1 = getattr(agent.ac, "fc1_impl", None)
     x6 = fc1 in PLANE_PRODUCTS
@@ -717,7 +767,7 @@ def main():
         "roofline": dict(roofline_of(dominant, kernels[dominant], fc1),
                          **({"note": "in the loop the weight gradient runs on a side stream beside conv3's "
                                      "backward segmented sums, so its event time includes that sharing; "
-                                     "alone: roofline_x6_standalone"}
+                                     "alone: roofline_x6_standalone (--full)"}
                             if dominant == "gemm_wgrad" and x6 and wgrad_side() else {})),
         # dominant hand-written kernel
         "roofline_handwritten": dict(roofline_of(handwritten, kernels[handwritten]),
@@ -728,7 +778,7 @@ def main():
         # fc1's GEMM form: h3 = f16 two-plane (3 products, error below hipBLASLt's fp32 GEMM), x6 = bf16 three-plane
         "fc1_impl": fc1,
         # the env-step kernel inside the timed loop (absent when the rollout replays as a graph:
-        # no per-kernel events inside it); the HBM-scale measurement is tiers.env_only_2M_envs
+        # no per-kernel events inside it); the HBM-scale measurement is tiers.env_only_2M_envs (--full)
         "roofline_env_step": roofline_of("k_env_step", kernels["k_env_step"]) if "k_env_step" in kernels else None,
         # whole iteration, counting the fp32 products actually computed (GEMMs of conv3 / fc1 / heads on the
         # evaluated frames and windows), against the ceiling of the instructions that compute them: with the h3 form
@@ -751,12 +801,15 @@ def main():
     }
     if rank_spread is not None:
         out["ranks"] = rank_spread
-    if x6 and agent.last_distinct_frac is not None:
+    # everything below takes runs of its own after the timed region: --full only
+    if args.full and x6 and agent.last_distinct_frac is not None:
         # the x6 GEMMs alone at the update's shape (distinct frames per minibatch)
         U = int(round(agent.last_distinct_frac * (B // args.minibatches)))
         out["roofline_x6_standalone"] = x6_standalone(torch, U, device, fc1)
     state["phase"] = "tiers"
-    if world > 1:
+    if not args.full:
+        pass
+    elif world > 1:
         out["tiers"] = "run at n_gpus=1 only (their agents' updates would all-reduce on the world group)"
     elif not args.no_tiers:
         floors = floor_tier(agent)
@@ -772,7 +825,7 @@ def main():
                         "hard_22": hard22_tier(device, N, T, args.epochs, args.minibatches),
                         "fomaml": fomaml_tier(device, args.difficulty)}
     state["phase"] = "cpu_baseline"
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
     print(json.dumps(out), flush=True)
     if dp.enabled:

@@ -19,7 +19,10 @@ def run(fast: bool, load=True):
     from test_gpu_obs_gae import pack
 
     dev = torch.device("cuda", 0)
-    g = np.load(os.path.join(REPO, "tests", "golden", "update_grad_ref.npz"))
+    sys.path.insert(0, os.path.join(REPO, "tests", "golden"))
+    from parts import load_parts
+
+    g = load_parts(os.path.join(REPO, "tests", "golden", "update_grad_ref"))
     B, MB, EP = (int(x) for x in g["cfg"])
     env = MerlinVecEnv(1, "mediumhard", seed=1, device=dev)
     perms = torch.from_numpy(g["perms"])

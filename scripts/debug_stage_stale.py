@@ -14,7 +14,10 @@ def main():
     from merlin.ppo import PPO
 
     dev = torch.device("cuda", 0)
-    g = np.load(os.path.join(REPO, "tests", "golden", "update_grad_ref.npz"))
+    sys.path.insert(0, os.path.join(REPO, "tests", "golden"))
+    from parts import load_parts
+
+    g = load_parts(os.path.join(REPO, "tests", "golden", "update_grad_ref"))
     env = MerlinVecEnv(1, "mediumhard", seed=1, device=dev)
     torch.manual_seed(0)
     agent = PPO(env, batch_size=8192, minibatch_size=2048, update_epochs=1, device=dev)

@@ -21,7 +21,8 @@ Sources, per fixture:
                   replay batch, with the randperm draws recorded for replay.
   update_rollout_ref.npz  the same on a real single-env rollout of the C oracle's env (repeated
                   observations, episode ends), the fixture the benched update path is pinned to.
-  update_grad_ref.npz  the REFERENCE PPO.update at a real minibatch size (8,192-step single-env rollout,
+  update_grad_ref.partKK.npz  (one fixture in parts, parts.py) the REFERENCE PPO.update at a real minibatch size
+                  (8,192-step single-env rollout,
                   minibatches of 2,048) with the first optimizer step's clipped gradient of every tensor
                   and that step's parameter change recorded whole (wrappers around the reference optimizer's
                   step and torch's clip_grad_norm_, defined here).
@@ -342,7 +343,7 @@ def gen_update_rollout():
 
 
 def gen_update_grad():
-    """update_grad_ref.npz: the REFERENCE PPO.update (src/ppo.py:122-168) at a real minibatch size -- an 8,192-step
+    """update_grad_ref.partKK.npz: the REFERENCE PPO.update (src/ppo.py:122-168) at a real minibatch size -- an 8,192-step
     single-env rollout of the C oracle's mediumhard env (seed 777, uniformly random actions, the env's own max_steps
     1,024), one epoch of 4 minibatches of 2,048 -- with the FIRST optimizer step's gradient recorded whole: a wrapper
     around the reference optimizer's `step` (after clip_grad_norm_, :153-155) saves every parameter's clipped
@@ -434,7 +435,11 @@ def gen_update_grad():
         out[f"p0_{i}"] = rec["p0"][i].numpy().astype(np.float32)
         out[f"grad{i}"] = g.numpy().astype(np.float32)  # the clipped gradient Adam consumed
         out[f"step{i}"] = (d.double() / 3e-4).numpy().astype(np.float16)  # the first Adam step in units of lr
-    np.savez_compressed(os.path.join(HERE, "update_grad_ref.npz"), **out)
+    # 5.4 MB compressed: committed as update_grad_ref.partKK.npz, each under the 1 MiB file limit (parts.py)
+    sys.path.insert(0, HERE)
+    from parts import save_parts
+
+    save_parts(os.path.join(HERE, "update_grad_ref"), out)
     print(f"update_grad_ref: {len(np.unique(codes, axis=0))} distinct frames of {B}, {int(dones.sum())} dones, "
           f"first-step norm {norms[0]:.5f}")
 

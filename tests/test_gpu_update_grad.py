@@ -1,6 +1,6 @@
 """GPU: the BENCHED update's gradient pinned to the reference's own gradient at a real minibatch size.
 
-`update_grad_ref.npz` (tests/golden/make_golden.py gen_update_grad) holds the reference PPO.update
+`update_grad_ref.part*.npz` (tests/golden/make_golden.py gen_update_grad) holds the reference PPO.update
 (src/ppo.py:122-168) on an 8,192-step single-env rollout of the C oracle's mediumhard env, one epoch of four
 minibatches of 2,048, with the FIRST optimizer step recorded whole: the starting weights, every parameter's clipped
 gradient as clip_grad_norm_ left it for Adam (:153-156), the pre-clip norm, the parameters' change by that step, and
