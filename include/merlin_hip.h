@@ -63,7 +63,8 @@
  * merlin_ppo_loss*, merlin_tower_head_bwd_planes, merlin_h3_gemm_nt_planes (cfg 62),
  * merlin_h3_gemm_tn_gather_planes_a (cfg 20), merlin_segment_sum_* (R / S / dQ / dT2), merlin_stage_*,
  * merlin_clip_adam.  The rest serve the other drop-in paths -- the gym single env and the frame path (obs
- * expansion, conv1 / conv2 lookups per frame, im2col), the autograd window path, FOMAML (merlin_group_act) -- or
+ * expansion, conv1 / conv2 lookups per frame, im2col), the autograd window path, FOMAML (merlin_group_act), few-shot
+ * evaluation (merlin_group_clip_sgd, merlin_episode_loss: src/distribution_over_tasks.py:97-128, :200-203) -- or
  * are ALTERNATE forms kept selectable for A/B and float64 precision tests: merlin_x6_* (fc1 in six bf16
  * products, rounds 2-3), merlin_h3_gemm_nt / _tn / _tn_planes / _nt_gather with the register-staged
  * configurations (round 4).  Probe-only configurations (kernel ablations that compute wrong results on purpose)
@@ -715,6 +716,31 @@ int64_t merlin_clip_adam_workspace(int32_t n_tensors, const int64_t *numel);
 int merlin_clip_adam(int32_t n_tensors, float *const *params, float *const *grads, float *const *exp_avg,
                      float *const *exp_avg_sq, float *const *steps, const int64_t *numel, double lr, double beta1,
                      double beta2, double eps, float max_norm, float *norm_out, double *workspace, void *stream);
+
+/* Few-shot evaluation's inner step (src/distribution_over_tasks.py:200-203, src/fomaml.py:180-182:
+ * clip_grad_norm_(fast.parameters(), max_norm) then SGD(lr).step()) for G independent parameter sets at once,
+ * csrc/merlin_fewshot.hip, two launches.  params / grads are host arrays of n_tensors (1..32) device pointers,
+ * tensor i float32[G][numel[i]] contiguous (task g's copy at g * numel[i]), numel[i] > 0.  Per task g:
+ * norm = ||g's gradients||_2 (f64 sums, rounded to float), coef = min(max_norm / (norm + 1e-6), 1) with a NaN
+ * kept, grads *= coef (written back, as clip_grad_norm_ does), params -= lr * grads.  Tasks never mix: a
+ * non-finite gradient turns only its own task's parameters NaN.  No atomics: bitwise reproducible.  norm_out
+ * float32[G] (NULL: not written) gets the pre-clip norms.  workspace
+ * double[merlin_group_clip_sgd_workspace(n_tensors, numel, G)] (-1: bad arguments).  n_tensors = 0 or G = 0:
+ * MERLIN_OK without a launch. */
+int64_t merlin_group_clip_sgd_workspace(int32_t n_tensors, const int64_t *numel, int32_t G);
+int merlin_group_clip_sgd(int32_t n_tensors, float *const *params, float *const *grads, const int64_t *numel,
+                          int32_t G, float lr, float max_norm, float *norm_out, double *workspace, void *stream);
+
+/* The per-episode loss of src/distribution_over_tasks.py:97-128 for n episodes stored [T][n] (row t, episode i at
+ * t * n + i), episode i of length_dev[i] steps (int32, clamped to 1..T), one launch.  Over the episode's own steps
+ * only: GAE backwards in merlin_gae's fp32 order with the bootstrap masked at the last step (the advantages,
+ * written to workspace_dev float[T][n], equal merlin_gae's with done = 1 at the last step), mean and unbiased
+ * standard deviation of the advantages (f64), adv_n = (adv - mean) / (std + 1e-8) (zeros for a 1-step episode),
+ * ret = value + adv_n, loss_dev[i] = -mean(new_logp) + 0.5 * mean((new_value - ret)^2) (f64 sums).  Entries at
+ * t >= length are neither read nor written. */
+int merlin_episode_loss(const float *reward_dev, const float *value_dev, const float *new_logp_dev,
+                        const float *new_value_dev, const int32_t *length_dev, int32_t T, int32_t n, double gamma,
+                        double lam, float *workspace_dev, float *loss_dev, void *stream);
 
 #ifdef __cplusplus
 }

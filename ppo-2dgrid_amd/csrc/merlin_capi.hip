@@ -1312,4 +1312,40 @@ int merlin_clip_adam(int32_t n_tensors, float *const *params, float *const *grad
     return MERLIN_OK;
 }
 
+int64_t merlin_group_clip_sgd_workspace(int32_t n_tensors, const int64_t *numel, int32_t G) {
+    if (n_tensors < 0 || n_tensors > merlin::OPT_MAX_TENSORS || G < 0 || (n_tensors > 0 && !numel)) return -1;
+    for (int i = 0; i < n_tensors; i++)
+        if (numel[i] <= 0) return -1;
+    return std::max<int64_t>(1, merlin::group_blocks(n_tensors, numel) * (int64_t)G);
+}
+
+int merlin_group_clip_sgd(int32_t n_tensors, float *const *params, float *const *grads, const int64_t *numel,
+                          int32_t G, float lr, float max_norm, float *norm_out, double *workspace, void *stream) {
+    if (n_tensors < 0 || n_tensors > merlin::OPT_MAX_TENSORS)
+        return fail(MERLIN_E_INVALID, "n_tensors must be in [0, 32]");
+    if (G < 0 || G > 65535) return fail(MERLIN_E_INVALID, "G must be in [0, 65535]");
+    if (n_tensors == 0 || G == 0) return MERLIN_OK;
+    if (!params || !grads || !numel || !workspace) return fail(MERLIN_E_INVALID, "null argument");
+    for (int i = 0; i < n_tensors; i++) {
+        if (numel[i] <= 0) return fail(MERLIN_E_INVALID, "every tensor needs numel > 0");
+        if (!params[i] || !grads[i]) return fail(MERLIN_E_INVALID, "null tensor pointer");
+    }
+    if (merlin::group_blocks(n_tensors, numel) > INT32_MAX / 2) return fail(MERLIN_E_INVALID, "too many elements");
+    HIP_TRY(merlin::launch_group_clip_sgd(n_tensors, params, grads, numel, G, lr, max_norm, norm_out, workspace,
+                                          (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_episode_loss(const float *reward, const float *value, const float *new_logp, const float *new_value,
+                        const int32_t *length, int32_t T, int32_t n, double gamma, double lam, float *workspace,
+                        float *loss, void *stream) {
+    if (T < 1 || n < 0) return fail(MERLIN_E_INVALID, "episode_loss needs T >= 1 and n >= 0");
+    if (n == 0) return MERLIN_OK;
+    if (!reward || !value || !new_logp || !new_value || !length || !workspace || !loss)
+        return fail(MERLIN_E_INVALID, "null argument");
+    HIP_TRY(merlin::launch_episode_loss(reward, value, new_logp, new_value, length, T, n, gamma, lam, workspace, loss,
+                                        (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
 }  // extern "C"

@@ -450,4 +450,13 @@ hipError_t launch_clip_adam(int n, float *const *params, float *const *grads, fl
                             float *const *exp_avg_sq, float *const *steps, const int64_t *numel, double lr, double beta1,
                             double beta2, double eps, float max_norm, float *norm_out, double *partial, hipStream_t s);
 
+// few-shot evaluation's reductions (merlin_fewshot.hip): per-task clip_grad_norm_ + SGD over stacked parameter
+// sets float[G][numel[i]], and the per-episode GAE / normalisation / loss of [T][n] episodes
+int64_t group_blocks(int n, const int64_t *numel);  // blocks per task
+hipError_t launch_group_clip_sgd(int n, float *const *params, float *const *grads, const int64_t *numel, int G,
+                                 float lr, float max_norm, float *norm_out, double *partial, hipStream_t s);
+hipError_t launch_episode_loss(const float *rew, const float *val, const float *nlp, const float *nval,
+                               const int32_t *length, int T, int N, double gamma, double lam, float *adv_ws,
+                               float *loss, hipStream_t s);
+
 }  // namespace merlin

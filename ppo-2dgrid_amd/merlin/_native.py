@@ -177,6 +177,10 @@ def lib():
     L.merlin_window_gemm_bwd_work.argtypes = [i32, i64]
     L.merlin_window_gemm_bwd_work.restype = i64
     L.merlin_window_gemm_bwd.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp, vp, vp, i64, vp]
+    L.merlin_group_clip_sgd_workspace.argtypes = [i32, vp, i32]
+    L.merlin_group_clip_sgd_workspace.restype = i64
+    L.merlin_group_clip_sgd.argtypes = [i32, vp, vp, vp, i32, C.c_float, C.c_float, vp, vp, vp]
+    L.merlin_episode_loss.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp]
     check_env_config_layout(L)
     _lib = L
     return L
@@ -226,6 +230,7 @@ EXPORTED_SYMBOLS = (
     "merlin_h3_gemm_tn_gather_planes_a", "merlin_h3_gemm_nt_heads_planes", "merlin_h3_gemm_tn_gather_planes",
     "merlin_tower_window_conv3_planes", "merlin_window_gemm_bwd_work", "merlin_window_gemm_bwd",
     "merlin_window_gemm_fwd",
+    "merlin_group_clip_sgd_workspace", "merlin_group_clip_sgd", "merlin_episode_loss",
 )
 
 
@@ -1483,3 +1488,63 @@ def clip_adam(params, grads, exp_avgs, exp_avg_sqs, steps, lr, beta1, beta2, eps
                                  float(lr), float(beta1), float(beta2), float(eps), float(max_norm), ptr(norm_out),
                                  ptr(workspace), stream_of(params[0])), "merlin_clip_adam")
     return norm_out
+
+
+def group_clip_sgd(params, grads, lr, max_norm, norm_out=None, workspace=None):
+    """clip_grad_norm_(max_norm) + SGD(lr).step() for G independent parameter sets in two launches
+    (merlin_group_clip_sgd): params[i] / grads[i] float32 [G, *shape_i]; per task the gradients are clipped
+    in place and params -= lr * grads.  Returns the tasks' pre-clip norms float32[G] (norm_out)."""
+    n = len(params)
+    if len(grads) != n:
+        raise ValueError("group_clip_sgd: parameter / gradient lists differ in length")
+    if n == 0:
+        return norm_out
+    if n > 32:
+        raise ValueError("group_clip_sgd: at most 32 tensors")
+    G = int(params[0].shape[0])
+    for p, g in zip(params, grads):
+        if p.dtype != torch.float32 or g.dtype != torch.float32:
+            raise MerlinNativeError("group_clip_sgd: float32 tensors only")
+        if p.dim() < 1 or p.shape != g.shape or int(p.shape[0]) != G:
+            raise ValueError("group_clip_sgd: every parameter and gradient is [G, *shape] with the same G")
+    dev = params[0].device
+    if norm_out is None:
+        norm_out = torch.empty(G, dtype=torch.float32, device=dev)
+    if G == 0:
+        return norm_out
+    if norm_out.dtype != torch.float32 or norm_out.numel() != G:
+        raise ValueError("group_clip_sgd: norm_out is float32[G]")
+    numel = (C.c_int64 * n)(*[int(p.numel() // G) for p in params])
+    arr = lambda ts: (C.c_void_p * n)(*[ptr(t).value for t in ts])  # noqa: E731
+    need = int(lib().merlin_group_clip_sgd_workspace(n, numel, G))
+    if need < 0:
+        raise ValueError("group_clip_sgd: empty tensors are not supported")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=dev)
+    if workspace.dtype != torch.float64 or workspace.numel() < need:
+        raise ValueError(f"group_clip_sgd: workspace is float64[{need}]")
+    check(lib().merlin_group_clip_sgd(n, arr(params), arr(grads), numel, G, float(lr), float(max_norm), ptr(norm_out),
+                                      ptr(workspace), stream_of(params[0])), "merlin_group_clip_sgd")
+    return norm_out
+
+
+def episode_loss(reward, value, new_logp, new_value, length, gamma, lam, workspace=None, out=None):
+    """The per-episode loss of src/distribution_over_tasks.py:97-128 in one launch (merlin_episode_loss): the four
+    float32 [T, n] tensors hold n episodes, episode i's first length[i] (int32, 1..T) rows; later rows are not
+    read.  Returns loss float32[n]; workspace float32 [T, n] receives the episodes' (unnormalised) advantages."""
+    T, n = (int(x) for x in reward.shape)
+    for t in (reward, value, new_logp, new_value):
+        if t.dtype != torch.float32 or tuple(t.shape) != (T, n):
+            raise ValueError("episode_loss: reward / value / new_logp / new_value are float32 [T, n]")
+    if length.dtype != torch.int32 or length.numel() != n:
+        raise ValueError("episode_loss: length is int32[n]")
+    if workspace is None:
+        workspace = torch.empty((T, n), dtype=torch.float32, device=reward.device)
+    if workspace.dtype != torch.float32 or workspace.numel() != T * n:
+        raise ValueError("episode_loss: workspace is float32 [T, n]")
+    out = torch.empty(n, dtype=torch.float32, device=reward.device) if out is None else out
+    assert out.dtype == torch.float32 and out.numel() == n
+    check(lib().merlin_episode_loss(ptr(reward), ptr(value), ptr(new_logp), ptr(new_value), ptr(length), T, n,
+                                    float(gamma), float(lam), ptr(workspace), ptr(out), stream_of(reward)),
+          "merlin_episode_loss")
+    return out

@@ -18,6 +18,9 @@
                      masked out, advantages normalised over the episode (zeros for a 1-step
                      episode), returns = values + advantages, then -mean(logp) + 0.5 * mean((v -
                      return)^2) with the episode's observations re-evaluated.
+``evaluate_few_shot`` src/distribution_over_tasks.py:132-209 for many seeds, a chunk of tasks at a time: per-task
+                     adaptation on sampled support rollouts, then the scored deterministic episode
+                     (merlin/few_shot.py).
 """
 from __future__ import annotations
 
@@ -138,6 +141,43 @@ def evaluate_zero_shot(ac, seeds, difficulty: str = "mediumhard", size: int = 16
         0, env_of, ((new_v - ret.reshape(-1)[sel]) ** 2).double()) / cnt
     loss = (-lp_mean + 0.5 * v_err).float()
     return total.cpu().tolist(), steps.cpu().tolist(), loss.cpu().tolist()
+
+
+def evaluate_few_shot(ac, seeds, adapt_steps: int, lr_inner: float = 0.01, k_support: int = 256,
+                      difficulty: str = "mediumhard", size: int = 16, device="cuda", max_steps: int | None = None,
+                      task_batch: int = 32, **env_flags):
+    """(rewards list[float], steps list[int], losses list[float]) of src/distribution_over_tasks.py:132-209 for
+    many seeds: per seed, a copy of ``ac`` takes ``adapt_steps`` clipped SGD(lr_inner) steps, each on a fresh support
+    rollout of ``k_support`` sampled steps of that seed's map, then plays one deterministic episode
+    (merlin.few_shot.FewShotAdapter).  The seeds are processed ``task_batch`` at a time, the last chunk padded by
+    repeating its last seed (its padded results dropped), so one rollout shape -- one HIP graph -- serves every chunk.
+    adapt_steps = 0 scores ``ac`` itself, as evaluate_zero_shot does.
+
+    The support rollouts' draws are keyed by a seed taken from torch's generator when this function starts, the
+    rollout counter, the step and the task's position in its chunk: the same torch.manual_seed and the same calls
+    give identical results, and moving a seed to another position (another task_batch) changes its draws."""
+    from .few_shot import FewShotAdapter
+
+    seeds = [int(s) for s in seeds]
+    rewards, steps, losses = [], [], []
+    if not seeds:
+        return rewards, steps, losses
+    B = max(1, min(int(task_batch), len(seeds)))
+    ad = FewShotAdapter(ac, lr_inner=lr_inner, difficulty=difficulty, size=size, device=device, max_steps=max_steps,
+                        **env_flags)
+    try:
+        for c0 in range(0, len(seeds), B):
+            chunk = seeds[c0:c0 + B]
+            m = len(chunk)
+            chunk = chunk + [chunk[-1]] * (B - m)
+            params = ad.adapt(chunk, int(adapt_steps), int(k_support))
+            r, s, ls = ad.episode(params, chunk)
+            rewards += r[:m]
+            steps += s[:m]
+            losses += ls[:m]
+    finally:
+        ad.close()
+    return rewards, steps, losses
 
 
 def evaluate_policy(ac, difficulty: str = "mediumhard", episodes: int = 3, seed: int | None = None,

@@ -42,15 +42,18 @@ CAPTURE_AFTER = 2
 
 
 class FOMAML:
-    def __init__(self, scenario_creator, lr_inner=0.01, lr_outer=3e-4, device="cuda", difficulty="medium"):
+    def __init__(self, scenario_creator, lr_inner=0.01, lr_outer=3e-4, device="cuda", difficulty="medium",
+                 meta_policy=None, env_kwargs=None):
+        """meta_policy / env_kwargs: an existing CNNActorCritic on the device as the meta policy, and the task envs'
+        constructor arguments instead of the scenario creator's (merlin.few_shot adapts a trained policy)."""
         self.sc = scenario_creator
         self.difficulty = difficulty
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise nat.MerlinNativeError("merlin.FOMAML runs its rollouts/GAE as HIP kernels; pass a GPU device")
         self.lr_inner = lr_inner
-        self.env_kwargs = self.sc._env_kwargs(difficulty)
-        self.meta_policy = CNNActorCritic((56, 56, 3), 3).to(self.device)
+        self.env_kwargs = self.sc._env_kwargs(difficulty) if env_kwargs is None else dict(env_kwargs)
+        self.meta_policy = CNNActorCritic((56, 56, 3), 3).to(self.device) if meta_policy is None else meta_policy
         # capturable: the step count lives on the device, so the Adam step can be part of a captured graph
         self.meta_optimizer = optim.Adam(self.meta_policy.parameters(), lr=lr_outer, capturable=True)
         self.capture_steps = CAPTURE_STEPS
