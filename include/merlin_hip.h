@@ -85,7 +85,7 @@ extern "C" {
 #define MERLIN_E_INVALID 1     /* bad argument / config */
 #define MERLIN_E_HIP 2         /* a HIP runtime call failed */
 #define MERLIN_E_DEVICE 3      /* device-side error flag raised (see merlin_env_errors) */
-#define MERLIN_E_UNSUPPORTED 4 /* e.g. grid size > 32 */
+#define MERLIN_E_UNSUPPORTED 4 /* e.g. grid size outside 5..32, hardest below size 8 */
 
 /* difficulty ids (ScenarioCreator difficulties, src/config/scenario.yaml) */
 #define MERLIN_EASY 0
@@ -117,7 +117,8 @@ typedef struct merlin_env merlin_env;
 
 typedef struct {
     int32_t num_envs;          /* envs in this context (this rank's shard) */
-    int32_t size;              /* grid side, 5..32 (reference: 16, base_env.py:17) */
+    int32_t size;              /* grid side, 5..32 (reference: 16, base_env.py:17); hardest: 8..32, the sizes at
+                                  which the reference's generator runs (hardest_env.py draws integers(2, size/2 - 1)) */
     int32_t difficulty;        /* MERLIN_* difficulty id */
     int32_t max_steps;         /* <= 0: 4*size^2 (base_env.py:32-33) */
     int32_t stuck_penalty;     /* 1: StuckPenaltyWrapper semantics (off in the reference chain) */

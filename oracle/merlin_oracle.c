@@ -542,10 +542,19 @@ void o_batch_rollout(int n, int size, int difficulty, int max_steps, const uint6
                      const int64_t *actions, int stuck_on, int explore_on, double explore_bonus,
                      uint8_t *codes_out, float *reward_out, uint8_t *term_out, uint8_t *trunc_out,
                      int32_t *agent_out) {
+    /* StuckPenaltyWrapper's defaults (stuck_penalty_wrapper.py:12) */
+    o_batch_rollout_stuck(n, size, difficulty, max_steps, seeds, steps, actions, stuck_on, 3, -0.1, explore_on,
+                          explore_bonus, codes_out, reward_out, term_out, trunc_out, agent_out);
+}
+
+void o_batch_rollout_stuck(int n, int size, int difficulty, int max_steps, const uint64_t *seeds, int steps,
+                           const int64_t *actions, int stuck_on, int max_stay, double penalty, int explore_on,
+                           double explore_bonus, uint8_t *codes_out, float *reward_out, uint8_t *term_out,
+                           uint8_t *trunc_out, int32_t *agent_out) {
     for (int i = 0; i < n; i++) {
         o_env e;
         o_env_init(&e, size, difficulty, max_steps);
-        o_env_set_stuck(&e, stuck_on, 3, -0.1);
+        o_env_set_stuck(&e, stuck_on, max_stay, penalty);
         o_env_set_explore(&e, explore_on, explore_bonus);
         o_env_reset(&e, 1, seeds[i]);
         if (codes_out) o_env_view_codes(&e, codes_out + (size_t)i * 49);

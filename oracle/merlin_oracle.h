@@ -83,6 +83,11 @@ void o_batch_rollout(int n, int size, int difficulty, int max_steps, const uint6
                      uint8_t *codes_out /* [(steps+1)][n][49] */,
                      float *reward_out, uint8_t *term_out, uint8_t *trunc_out,
                      int32_t *agent_out /* [(steps+1)][n][4]: x,y,dir,step_count */);
+/* the same with StuckPenaltyWrapper's max_stay / penalty given (o_batch_rollout: its defaults 3, -0.1) */
+void o_batch_rollout_stuck(int n, int size, int difficulty, int max_steps, const uint64_t *seeds,
+                           int steps, const int64_t *actions, int stuck_on, int max_stay, double penalty,
+                           int explore_on, double explore_bonus, uint8_t *codes_out, float *reward_out,
+                           uint8_t *term_out, uint8_t *trunc_out, int32_t *agent_out);
 /* grid dump after reset(seed) : cell[size*size]; meta6 = agent x,y,dir, goal x,y, attempts */
 void o_gen_map(int size, int difficulty, uint64_t seed, uint8_t *cells, int32_t *meta6);
 /* expand tile codes to uint8 HWC (56,56,3) using a 5x8x8x3 atlas */

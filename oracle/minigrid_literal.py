@@ -315,6 +315,39 @@ class LiteralEnv:
         return out
 
 
+class LiteralStuckPenalty:
+    """StuckPenaltyWrapper (src/wrappers/stuck_penalty_wrapper.py:3-57) around a LiteralEnv, restated: a counter of
+    consecutive steps that left the agent on the same cell -- turning and walking into a wall both count -- and
+    ``penalty`` added to the step's reward once the counter has reached ``max_stay``.  The counter and the
+    remembered position start afresh at every reset; the step compares the position after the inner step with the
+    remembered one, counts or clears, applies the penalty, then remembers the new position."""
+
+    def __init__(self, env: LiteralEnv, max_stay=3, penalty=-0.1):
+        self.env = env
+        self.max_stay = max_stay
+        self.penalty = penalty
+        self.stay_counter = 0
+        self.last_pos = None
+
+    def reset(self, seed=None):
+        codes = self.env.reset(seed)
+        self.stay_counter = 0
+        self.last_pos = tuple(self.env.agent_pos)
+        return codes
+
+    def step(self, action):
+        codes, reward, terminated, truncated = self.env.step(action)
+        pos = tuple(self.env.agent_pos)
+        if pos == self.last_pos:
+            self.stay_counter += 1
+        else:
+            self.stay_counter = 0
+        if self.stay_counter >= self.max_stay:
+            reward += self.penalty
+        self.last_pos = pos
+        return codes, reward, terminated, truncated
+
+
 def full_obs_from_state(walls, agent_pos, agent_dir, goal_pos, size):
     """The same observation from the bit-row state MerlinVecEnv.get_state reports (walls[y] bit x = wall at
     (x, y)): the checker of merlin_env_full_obs."""

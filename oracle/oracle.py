@@ -31,7 +31,9 @@ class PCG64State(C.Structure):
 
 
 def build(force: bool = False) -> str:
-    if force or not os.path.exists(LIB_PATH):
+    srcs = [os.path.join(HERE, f) for f in ("merlin_oracle.c", "merlin_oracle.h")]
+    stale = not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
+    if force or stale:  # a library older than its sources lacks what they added
         subprocess.run(["make", "-s", "-C", HERE] + (["-B"] if force else []), check=True)
     return LIB_PATH
 
@@ -56,6 +58,8 @@ def lib():
         L.o_choice_noreplace.argtypes = [P(PCG64State), C.c_int64, C.c_int64, vp]
         L.o_batch_rollout.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int,
                                       C.c_int, C.c_double, vp, vp, vp, vp, vp]
+        L.o_batch_rollout_stuck.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int,
+                                            C.c_double, C.c_int, C.c_double, vp, vp, vp, vp, vp]
         L.o_gen_map.argtypes = [C.c_int, C.c_int, C.c_uint64, vp, vp]
         L.o_render.argtypes = [vp, C.c_int, vp, vp]
         L.o_gae_f32_tn.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp]
@@ -98,8 +102,9 @@ def gen_map(size: int, difficulty: str, seed: int):
 
 
 def batch_rollout(seeds, actions, size=16, difficulty="mediumhard", max_steps=0, stuck=False,
-                  explore=False, explore_bonus=0.0):
+                  explore=False, explore_bonus=0.0, max_stay=3, penalty=-0.1):
     """Env i: reset(seed=seeds[i]) then steps actions[t, i] with unseeded auto-reset.
+    max_stay / penalty: StuckPenaltyWrapper's parameters (used with stuck=True; its defaults).
 
     Returns codes[T+1, n, 49] (obs after reset / after each step), reward[T, n] f32,
     term[T, n] u8, trunc[T, n] u8, agent[T+1, n, 4] (x, y, dir, step_count).
@@ -113,9 +118,9 @@ def batch_rollout(seeds, actions, size=16, difficulty="mediumhard", max_steps=0,
     term = np.zeros((T, n), dtype=np.uint8)
     trunc = np.zeros((T, n), dtype=np.uint8)
     agent = np.zeros((T + 1, n, 4), dtype=np.int32)
-    lib().o_batch_rollout(n, size, DIFFICULTIES[difficulty], max_steps, _p(seeds), T, _p(actions),
-                          int(stuck), int(explore), float(explore_bonus), _p(codes), _p(rew),
-                          _p(term), _p(trunc), _p(agent))
+    lib().o_batch_rollout_stuck(n, size, DIFFICULTIES[difficulty], max_steps, _p(seeds), T, _p(actions),
+                                int(stuck), int(max_stay), float(penalty), int(explore), float(explore_bonus),
+                                _p(codes), _p(rew), _p(term), _p(trunc), _p(agent))
     return codes, rew, term, trunc, agent
 
 

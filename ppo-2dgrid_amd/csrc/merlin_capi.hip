@@ -302,10 +302,11 @@ int merlin_env_create(const merlin_env_config *cfg, merlin_env **out) {
         return fail(MERLIN_E_UNSUPPORTED, "grid size must be in [5, 32]");
     if (cfg->difficulty < MERLIN_EASY || cfg->difficulty > MERLIN_HARDEST)
         return fail(MERLIN_E_INVALID, "unknown difficulty");
-    if (cfg->difficulty == MERLIN_HARDEST && cfg->size < 9)
-        return fail(MERLIN_E_UNSUPPORTED, "hardest needs size >= 9 (integers(2, mid-1))");
-    if (cfg->difficulty == MERLIN_HARD && cfg->size < 6)
-        return fail(MERLIN_E_UNSUPPORTED, "hard needs size >= 6");
+    // the sizes at which the reference's generators run: every other difficulty (hard included: one gap, the goal
+    // and the agent each have a free column at 5) generates from 5 up; hardest draws integers(2, size/2 - 1) for its
+    // first opening, an empty range below 8 (numpy raises ValueError)
+    if (cfg->difficulty == MERLIN_HARDEST && cfg->size < 8)
+        return fail(MERLIN_E_UNSUPPORTED, "hardest needs size >= 8 (integers(2, size/2 - 1) is empty below)");
     DeviceWs *ws = nullptr;
     int rc = device_ws(&ws);
     if (rc) return rc;

@@ -271,7 +271,10 @@ struct Grid {
         place_goal(r);
     }
 
-    // EasyEnv._gen_grid (easy_env.py:19-39): put_obj(Goal, W-5, H-5) may sit on the agent
+    // EasyEnv._gen_grid (easy_env.py:19-39): put_obj(Goal, W-5, H-5) may sit on the agent.  Grid.set replaces what
+    // the cell held: at size 5 that is the border wall's corner (0, 0), which becomes the goal -- shown as the goal
+    // tile, transparent, (8, 1, 0) in the full observation -- so its wall bit goes (no interior cell is 4-adjacent
+    // to a corner: the agent still cannot step there, and the stored rows are all the state there is)
     template <class R>
     __device__ void gen_easy(R &r) {
         walled();
@@ -279,6 +282,7 @@ struct Grid {
         gx = S - 5;
         gy = S - 5;
         goal_set = true;
+        if (S == 5) clear_wall(gx, gy);
     }
 
     // MediumEnv._gen_grid (medium_env.py:19-33)

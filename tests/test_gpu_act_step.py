@@ -1,7 +1,8 @@
 """GPU: the rollout's draw fused into the env step (merlin_env_act_step, round 5) against the two launches it replaces
 (merlin_act_draw, then merlin_env_step): the same actions / log-probs / values and the same env trajectory bit for
 bit, over many steps with frequent episode ends (short max_steps, so resets take look-ahead slots and, when a slot is
-empty, take the k_env_fallback path), sampled and deterministic, 16x16 and the 22x22 layout."""
+empty, take the k_env_fallback path), sampled and deterministic, 16x16, the 22x22 layout and the edge
+sizes (5, gen_hard's small-grid generator at 10, 32)."""
 import pytest
 import torch
 
@@ -9,7 +10,8 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("difficulty,size,det", [("mediumhard", 16, False), ("mediumhard", 16, True),
-                                                 ("hard", 22, False)])
+                                                 ("hard", 22, False), ("easy", 5, False),
+                                                 ("hardest", 32, False), ("hard", 10, True)])
 def test_act_step_matches_draw_then_step(device, difficulty, size, det):
     from merlin import MerlinVecEnv
     from merlin import _native as nat

@@ -62,6 +62,22 @@ def test_errors_are_reported_not_thrown():
     assert L.merlin_env_create(C.byref(cfg), C.byref(h)) == 4  # size > 32 unsupported
 
 
+def test_env_create_refuses_what_the_reference_cannot_generate():
+    """Host-side refusals of merlin_env_create (before any device call): sizes outside 5..32, and hardest below 8,
+    where the reference's generator draws from an empty range (tests/test_oracle_sizes.py::test_where_generators_stop).
+    The accepted boundary (hard at 5, hardest at 8) needs a device: tests/test_gpu_env_sizes.py."""
+    import ctypes as C
+
+    from merlin import _native as nat
+
+    L = nat.lib()
+    h = C.c_void_p()
+    for size, diff in [(4, 2), (33, 2), (4, 3), (7, 4), (6, 4), (5, 4)]:
+        cfg = nat.EnvConfig(4, size, diff, 0, 0, 3, -0.1, 0, 0.0)
+        assert L.merlin_env_create(C.byref(cfg), C.byref(h)) == 4, (size, diff)  # MERLIN_E_UNSUPPORTED
+    assert b"hardest" in L.merlin_last_error()
+
+
 def test_act_heads_draw_requires_epoch_counter():
     """a sampled action without the epoch counter would repeat its draws every call."""
     import torch
