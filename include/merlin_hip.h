@@ -151,6 +151,17 @@ int merlin_env_destroy(merlin_env *env);
 /* Seed env i with seeds_host[i] (numpy SeedSequence -> PCG64, as gymnasium
  * reset(seed=...)); takes effect at the next merlin_env_reset of that env. */
 int merlin_env_seed(merlin_env *env, const uint64_t *seeds_host, int32_t n, void *stream);
+/* Give env i the generator diff_host[i] (MERLIN_* ids); NULL restores the context's uniform difficulty.
+ * Takes effect at each env's next map generation: every look-ahead slot is invalidated, as merlin_env_seed does
+ * (the envs keep their current maps and RNG streams).  n != num_envs or an unknown id: MERLIN_E_INVALID;
+ * MERLIN_HARDEST on a context of size < 8: MERLIN_E_UNSUPPORTED, as merlin_env_create.  Stages from host memory
+ * and synchronises `stream` before returning.  The classes live in one device buffer allocated with the context,
+ * so launches captured into a HIP graph after the first assignment read later assignments without a re-capture;
+ * a capture made while the context was uniform (no buffer bound) does not.
+ * One lane generates one env's map, so a wave that holds several classes runs their generators one after
+ * another.  Every assignment is correct; assignments made of contiguous runs whose boundaries fall on multiples
+ * of 64 envs keep every wave of the full-width reset and refill passes on a single generator. */
+int merlin_env_set_difficulties(merlin_env *env, const int32_t *diff_host, int32_t n, void *stream);
 /* Reset the envs whose mask_dev[i] != 0 (mask_dev NULL = all), writing their
  * observation codes to obs_dev[i][8]; others' obs rows are left untouched. */
 int merlin_env_reset(merlin_env *env, const uint8_t *mask_dev, uint32_t *obs_dev, void *stream);
@@ -742,6 +753,17 @@ int merlin_group_clip_sgd(int32_t n_tensors, float *const *params, float *const 
 int merlin_episode_loss(const float *reward_dev, const float *value_dev, const float *new_logp_dev,
                         const float *new_value_dev, const int32_t *length_dev, int32_t T, int32_t n, double gamma,
                         double lam, float *workspace_dev, float *loss_dev, void *stream);
+
+/* Finished episodes of a rollout by class: rows t*N+i with done_dev[row] != 0 contribute their ep_return / ep_length
+ * to class class_dev[i] (< n_classes <= 8).  out_dev double[n_classes][4] = (episodes, sum return, sum return^2,
+ * sum length); accumulate != 0 adds to out_dev instead of overwriting.  csrc/merlin_epstats.hip, two launches: fp64
+ * sums in a fixed order, no atomics (two calls on the same input give the same bits), stream-ordered, no host
+ * sync, no allocation (the per-block sums live in the library's per-device workspace, so two calls on one device
+ * must be stream-ordered): safe inside a captured graph.  T = 0, N = 0 or a class with no finished episode: zeros
+ * for that class.  An env whose class is >= n_classes is ignored. */
+int merlin_episode_class_stats(const float *done_dev, const double *ep_return_dev, const int32_t *ep_length_dev,
+                               const uint8_t *class_dev, int32_t T, int32_t N, int32_t n_classes,
+                               double *out_dev, int32_t accumulate, void *stream);
 
 #ifdef __cplusplus
 }

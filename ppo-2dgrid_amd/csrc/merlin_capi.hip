@@ -23,6 +23,10 @@ struct merlin_env {
     // are left out (an empty slot would still raise MERLIN_DEVERR_SLOT_EMPTY); cleared when merlin_env_seed makes
     // the slots stale (round 6: FOMAML's 32-env task rollouts, two graph nodes fewer per step)
     bool seed_slots_full = false;
+    // the per-env generator classes uint8[n], allocated with the context so that its address never changes: dev.diff
+    // is this buffer once merlin_env_set_difficulties has assigned classes, null (the uniform dev.difficulty) before
+    // that and after a NULL assignment
+    uint8_t *diff_buf = nullptr;
 };
 
 namespace {
@@ -211,6 +215,7 @@ struct DeviceWs {
     float *epi_work = nullptr;   // GEMM epilogues: per-block column-sum partials
     double *stage_part = nullptr;  // conv tables' adjoint: the 625-combination type's partial dW2 sums
     uint32_t *tower_err = nullptr;  // device error flags of the tower kernels (merlin_tower_errors)
+    double *eps_part = nullptr;     // merlin_episode_class_stats: the per-block class sums
 };
 constexpr int MAX_DEV = 64;
 DeviceWs g_dev[MAX_DEV];
@@ -235,6 +240,7 @@ int device_ws(DeviceWs **out) {
         HIP_TRY(hipMalloc(&w.epi_work, sizeof(float) * merlin::epilogue_work_floats()));
         HIP_TRY(hipMalloc(&w.stage_part, sizeof(double) * merlin::STAGE_WS_DOUBLES));
         HIP_TRY(hipMalloc(&w.tower_err, sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&w.eps_part, sizeof(double) * merlin::EPS_MAX_BLOCKS * merlin::EPS_MAX_CLASSES * 4));
         HIP_TRY(hipMemset(w.tower_err, 0, sizeof(uint32_t)));  // once, outside any capture
         HIP_TRY(hipDeviceSynchronize());
         w.ready = true;
@@ -347,6 +353,7 @@ int merlin_env_create(const merlin_env_config *cfg, merlin_env **out) {
     alloc((void **)&d.rflag, n * sizeof(uint8_t));
     alloc((void **)&d.bflag, (n + 63) / 64);  // one flag per step block (merlin_env.hip SBLK >= 64 envs)
     if (d.explore_on) alloc((void **)&d.visited, n * d.sp * sizeof(uint32_t));
+    alloc((void **)&e->diff_buf, n * sizeof(uint8_t));
     if (err != hipSuccess) {
         merlin_env_destroy(e);
         return hip_fail(err, "hipMalloc(env state)");
@@ -359,7 +366,7 @@ int merlin_env_destroy(merlin_env *e) {
     if (!e) return MERLIN_OK;
     merlin::EnvDev &d = e->dev;
     void *ptrs[] = {d.walls, d.agent, d.rng_s, d.rng_i, d.rng_b, d.ep_ret, d.ep_len, d.err, d.visited,
-                    d.pg_walls, d.pg_agent, d.pg_rng_s, d.pg_rng_b, d.pg_valid, d.rflag, d.bflag};
+                    d.pg_walls, d.pg_agent, d.pg_rng_s, d.pg_rng_b, d.pg_valid, d.rflag, d.bflag, e->diff_buf};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     delete e;
@@ -392,6 +399,34 @@ int merlin_env_seed(merlin_env *e, const uint64_t *seeds, int32_t n, void *strea
     delete[] st;
     delete[] inc;
     if (err != hipSuccess) return hip_fail(err, "merlin_env_seed");
+    return MERLIN_OK;
+}
+
+int merlin_env_set_difficulties(merlin_env *e, const int32_t *diff, int32_t n, void *stream) {
+    if (!e) return fail(MERLIN_E_INVALID, "null env");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t N = (size_t)e->dev.n;
+    hipError_t err = hipSuccess;
+    uint8_t *host = nullptr;
+    if (diff) {
+        if (n != e->dev.n) return fail(MERLIN_E_INVALID, "difficulty count must equal num_envs");
+        for (size_t i = 0; i < N; i++) {
+            if (diff[i] < MERLIN_EASY || diff[i] > MERLIN_HARDEST) return fail(MERLIN_E_INVALID, "unknown difficulty");
+            if (diff[i] == MERLIN_HARDEST && e->dev.size < 8)  // merlin_env_create's rule
+                return fail(MERLIN_E_UNSUPPORTED, "hardest needs size >= 8 (integers(2, size/2 - 1) is empty below)");
+        }
+        host = new uint8_t[N];
+        for (size_t i = 0; i < N; i++) host[i] = (uint8_t)diff[i];
+        err = hipMemcpyAsync(e->diff_buf, host, N, hipMemcpyHostToDevice, s);
+        e->dev.diff = e->diff_buf;
+    } else {
+        e->dev.diff = nullptr;
+    }
+    if (err == hipSuccess) err = merlin::zero_async(e->dev.pg_valid, N, s);  // look-ahead maps are stale
+    e->seed_slots_full = false;
+    if (err == hipSuccess) err = hipStreamSynchronize(s);  // the host staging buffer is freed below
+    delete[] host;
+    if (err != hipSuccess) return hip_fail(err, "merlin_env_set_difficulties");
     return MERLIN_OK;
 }
 
@@ -1346,6 +1381,22 @@ int merlin_episode_loss(const float *reward, const float *value, const float *ne
         return fail(MERLIN_E_INVALID, "null argument");
     HIP_TRY(merlin::launch_episode_loss(reward, value, new_logp, new_value, length, T, n, gamma, lam, workspace, loss,
                                         (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_episode_class_stats(const float *done, const double *ep_return, const int32_t *ep_length,
+                               const uint8_t *cls, int32_t T, int32_t N, int32_t n_classes, double *out,
+                               int32_t accumulate, void *stream) {
+    if (T < 0 || N < 0) return fail(MERLIN_E_INVALID, "episode_class_stats needs T >= 0 and N >= 0");
+    if (n_classes < 1 || n_classes > merlin::EPS_MAX_CLASSES)
+        return fail(MERLIN_E_INVALID, "episode_class_stats needs n_classes in [1, 8]");
+    if (!out) return fail(MERLIN_E_INVALID, "null argument");
+    if (T > 0 && N > 0 && (!done || !ep_return || !ep_length || !cls)) return fail(MERLIN_E_INVALID, "null argument");
+    DeviceWs *ws = nullptr;
+    int rc = device_ws(&ws);
+    if (rc) return rc;
+    HIP_TRY(merlin::launch_episode_class_stats(done, ep_return, ep_length, cls, T, N, n_classes, out, accumulate,
+                                               ws->eps_part, (hipStream_t)stream));
     return MERLIN_OK;
 }
 

@@ -635,14 +635,22 @@ __device__ __forceinline__ bool take_slot(const EnvDev &E, int i, uint32_t (*row
     return true;
 }
 
+// Env i's generator: its class in the context's per-env buffer (merlin_env_set_difficulties), or the context's
+// uniform difficulty when there is none.  One lane generates one env's map, so a wave whose envs hold several classes
+// runs their generators one after another (the switch in Grid::generate diverges); any assignment is correct, and one
+// made of contiguous runs whose boundaries fall on multiples of 64 envs keeps every wave of the full-width passes
+// (k_env_reset, k_env_refill<SP, 1>) on one generator.  The packed passes (k_env_refill<SP, 4>, k_env_fallback) and the
+// multi-step kernel gather whichever envs finished, so their waves mix classes wherever the finished envs do.
+__device__ __forceinline__ int env_difficulty(const EnvDev &E, int i) { return E.diff ? (int)E.diff[i] : E.difficulty; }
+
 template <int SP, int NB, bool INL>
 __device__ __forceinline__ void take_map(const EnvDev &E, int i, uint32_t (*rows)[NB], int lane, GenOut &g) {
     if (!take_slot<SP, NB>(E, i, rows, lane, g)) {
         Rng r = load_rng(E, i);
         if (INL)
-            generate_map_inl<SP, NB>(rows, lane, E.size, E.difficulty, r, E.err + 1, g);
+            generate_map_inl<SP, NB>(rows, lane, E.size, env_difficulty(E, i), r, E.err + 1, g);
         else
-            generate_map<SP, NB>(rows, lane, E.size, E.difficulty, r, E.err + 1, g);
+            generate_map<SP, NB>(rows, lane, E.size, env_difficulty(E, i), r, E.err + 1, g);
         if (!E.reseed) store_rng(E, i, r);
     }
 }
@@ -684,7 +692,7 @@ template <int SP>
 __device__ __forceinline__ void refill_one(const EnvDev &E, int i, uint32_t (*rows)[BLK], int lane) {
     Rng r = load_rng(E, i);
     GenOut g;
-    generate_map_inl<SP, BLK>(rows, lane, E.size, E.difficulty, r, E.err + 1, g);
+    generate_map_inl<SP, BLK>(rows, lane, E.size, env_difficulty(E, i), r, E.err + 1, g);
     uint4 *dst = reinterpret_cast<uint4 *>(E.pg_walls + (size_t)i * SP);
 #pragma unroll
     for (int q = 0; q < SP / 4; q++) {

@@ -25,6 +25,7 @@ namespace merlin {
 //           pg_valid uint8[n] (1 = the slot holds the env's next map)
 //   rflag   uint8[n]        1 = reset due, its slot was empty (single-step launch; k_env_fallback)
 //   bflag   uint8[ceil(n/64)] 1 = some env of that step block (SBLK envs, merlin_env.hip) is flagged
+//   diff    uint8[n]        the env's map generator (MERLIN_* id); null = the uniform `difficulty`
 struct EnvDev {
     int n, size, sp, difficulty, max_steps;
     int stuck_on, max_stay;
@@ -48,6 +49,7 @@ struct EnvDev {
     uint8_t *pg_valid;
     uint8_t *rflag;
     uint8_t *bflag;
+    const uint8_t *diff;  // per-env generator class uint8[n] (merlin_env_set_difficulties); null: `difficulty` for all
 };
 
 // step launches between two look-ahead refills (merlin_env_step)
@@ -458,5 +460,12 @@ hipError_t launch_group_clip_sgd(int n, float *const *params, float *const *grad
 hipError_t launch_episode_loss(const float *rew, const float *val, const float *nlp, const float *nval,
                                const int32_t *length, int T, int N, double gamma, double lam, float *adv_ws,
                                float *loss, hipStream_t s);
+
+// finished episodes by env class (merlin_epstats.hip); partial = EPS_MAX_BLOCKS x EPS_MAX_CLASSES x 4 doubles
+constexpr int EPS_MAX_CLASSES = 8;
+constexpr int EPS_MAX_BLOCKS = 1024;
+hipError_t launch_episode_class_stats(const float *done, const double *ep_ret, const int32_t *ep_len,
+                                      const uint8_t *cls, int T, int N, int n_classes, double *out, int accumulate,
+                                      double *partial, hipStream_t s);
 
 }  // namespace merlin

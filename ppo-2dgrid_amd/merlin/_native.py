@@ -18,6 +18,7 @@ PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("MERLIN_HIP_LIB", os.path.join(PKG_ROOT, "lib", "libmerlin_hip.so"))
 
 MERLIN_OK = 0
+E_INVALID, E_HIP, E_DEVICE, E_UNSUPPORTED = 1, 2, 3, 4  # MERLIN_E_* of include/merlin_hip.h
 LAYOUT_NCHW = 0
 LAYOUT_NHWC = 1
 OBS_WORDS = 8
@@ -30,7 +31,7 @@ DIFFICULTY_IDS = {"easy": 0, "medium": 1, "mediumhard": 2, "hard": 3, "hardest":
 
 
 class MerlinNativeError(RuntimeError):
-    pass
+    code = None  # the MERLIN_E_* return code when a library call raised it (check)
 
 
 class EnvConfig(C.Structure):
@@ -78,6 +79,7 @@ def lib():
     L.merlin_env_create.argtypes = [C.POINTER(EnvConfig), C.POINTER(vp)]
     L.merlin_env_destroy.argtypes = [vp]
     L.merlin_env_seed.argtypes = [vp, u64p, i32, vp]
+    L.merlin_env_set_difficulties.argtypes = [vp, C.POINTER(C.c_int32), i32, vp]
     L.merlin_env_reset.argtypes = [vp, vp, vp, vp]
     L.merlin_env_step.argtypes = [vp, vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp]
     L.merlin_group_act.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp]
@@ -181,6 +183,7 @@ def lib():
     L.merlin_group_clip_sgd_workspace.restype = i64
     L.merlin_group_clip_sgd.argtypes = [i32, vp, vp, vp, i32, C.c_float, C.c_float, vp, vp, vp]
     L.merlin_episode_loss.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp]
+    L.merlin_episode_class_stats.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp]
     check_env_config_layout(L)
     _lib = L
     return L
@@ -231,6 +234,7 @@ EXPORTED_SYMBOLS = (
     "merlin_tower_window_conv3_planes", "merlin_window_gemm_bwd_work", "merlin_window_gemm_bwd",
     "merlin_window_gemm_fwd",
     "merlin_group_clip_sgd_workspace", "merlin_group_clip_sgd", "merlin_episode_loss",
+    "merlin_env_set_difficulties", "merlin_episode_class_stats",
 )
 
 
@@ -398,7 +402,9 @@ _NULL_SPAN = _NullSpan()
 def check(rc: int, what: str = "") -> None:
     if rc != MERLIN_OK:
         msg = lib().merlin_last_error().decode(errors="replace")
-        raise MerlinNativeError(f"{what or 'merlin call'} failed (code {rc}): {msg}")
+        err = MerlinNativeError(f"{what or 'merlin call'} failed (code {rc}): {msg}")
+        err.code = int(rc)
+        raise err
 
 
 def ptr(t: torch.Tensor | None):
@@ -1547,4 +1553,37 @@ def episode_loss(reward, value, new_logp, new_value, length, gamma, lam, workspa
     check(lib().merlin_episode_loss(ptr(reward), ptr(value), ptr(new_logp), ptr(new_value), ptr(length), T, n,
                                     float(gamma), float(lam), ptr(workspace), ptr(out), stream_of(reward)),
           "merlin_episode_loss")
+    return out
+
+
+MAX_EPISODE_CLASSES = 8
+
+
+def episode_class_stats(done, ep_return, ep_length, classes, n_classes, out=None, accumulate=False):
+    """Finished episodes of a rollout by env class (merlin_episode_class_stats, two launches, no host sync): done
+    float32 [T, N], ep_return float64 [T, N] and ep_length int32 [T, N] as the rollout buffer keeps them, classes
+    uint8[N].  Returns float64 [n_classes, 4] on the device: per class (episodes, sum of returns, sum of squared
+    returns, sum of lengths); accumulate=True adds to `out`.  fp64 sums in a fixed order: bitwise reproducible."""
+    if done.dim() != 2:
+        raise ValueError("episode_class_stats: done is float32 [T, N]")
+    T, N = (int(x) for x in done.shape)
+    if not 1 <= int(n_classes) <= MAX_EPISODE_CLASSES:
+        raise ValueError(f"episode_class_stats: n_classes in [1, {MAX_EPISODE_CLASSES}]")
+    if done.dtype != torch.float32 or ep_return.dtype != torch.float64 or ep_length.dtype != torch.int32:
+        raise ValueError("episode_class_stats: done float32, ep_return float64, ep_length int32")
+    if tuple(ep_return.shape) != (T, N) or tuple(ep_length.shape) != (T, N):
+        raise ValueError("episode_class_stats: ep_return / ep_length have done's shape [T, N]")
+    if classes.dtype != torch.uint8 or classes.numel() != N:
+        raise ValueError("episode_class_stats: classes is uint8[N]")
+    if out is None:
+        if accumulate:
+            raise ValueError("episode_class_stats: accumulate needs `out`")
+        out = torch.empty((int(n_classes), 4), dtype=torch.float64, device=done.device)
+    if out.dtype != torch.float64 or out.numel() != int(n_classes) * 4:
+        raise ValueError("episode_class_stats: out is float64 [n_classes, 4]")
+    with torch.cuda.device(done.device):
+        check(lib().merlin_episode_class_stats(ptr(done) if T * N else None, ptr(ep_return) if T * N else None,
+                                               ptr(ep_length) if T * N else None, ptr(classes) if N else None, T, N,
+                                               int(n_classes), ptr(out), int(bool(accumulate)), stream_of(done)),
+              "merlin_episode_class_stats")
     return out

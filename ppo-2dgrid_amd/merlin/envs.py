@@ -59,6 +59,10 @@ class MerlinVecEnv:
     stuck_penalty_wrapper.py:3-57; unwired in the reference, so off by default)
     and ``exploration_bonus`` (not defined by the reference; +``bonus`` the first
     time a cell is entered in an episode).
+
+    ``difficulty`` is one name for every env, or a sequence of ``num_envs`` names: env i then generates its maps with
+    ``difficulties[i]`` (merlin_env_set_difficulties; ``merlin.task_mix.assign`` builds wave-aligned assignments).
+    ``difficulty`` reads "mixed" when the envs differ, ``class_ids`` is the per-env MERLIN_* id on the device.
     """
 
     def __init__(self, num_envs: int, difficulty: str = "mediumhard", size: int = 16,
@@ -66,13 +70,17 @@ class MerlinVecEnv:
                  stuck_penalty: bool = False, max_stay: int = 3, penalty: float = -0.1,
                  exploration_bonus: bool = False, bonus: float = 0.01, env_offset: int = 0,
                  seeds=None, reseed_each_reset: bool = False, fully_observable: bool = False, flatten: bool = False):
-        if difficulty not in nat.DIFFICULTY_IDS:
+        self.num_envs = int(num_envs)
+        names = None if isinstance(difficulty, str) else self._check_names(difficulty)
+        if names is None and difficulty not in nat.DIFFICULTY_IDS:
             raise ValueError(f"Unknown difficulty: {difficulty}")
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise nat.MerlinNativeError("MerlinVecEnv runs on a GPU device (HIP); got " + str(device))
-        self.num_envs = int(num_envs)
-        self.difficulty = difficulty
+        # a per-env list: the context is created on its lowest class (every size that class runs at), the list set below
+        uniform = difficulty if names is None else min(names, key=nat.DIFFICULTY_IDS.__getitem__)
+        self.difficulty = uniform
+        self.difficulties = [uniform] * self.num_envs
         self.size = int(size)
         self.max_steps = int(max_steps) if max_steps else 4 * self.size * self.size
         self.env_offset = int(env_offset)
@@ -86,7 +94,7 @@ class MerlinVecEnv:
             shape = (int(np.prod(shape)),)
         self.single_observation_space = Box(0, 255, shape, np.uint8)
         self.observation_space = self.single_observation_space
-        cfg = nat.EnvConfig(self.num_envs, self.size, nat.DIFFICULTY_IDS[difficulty], self.max_steps,
+        cfg = nat.EnvConfig(self.num_envs, self.size, nat.DIFFICULTY_IDS[uniform], self.max_steps,
                             int(stuck_penalty), int(max_stay), float(penalty), int(exploration_bonus),
                             float(bonus), int(reseed_each_reset))
         self._lib = nat.lib()
@@ -95,6 +103,14 @@ class MerlinVecEnv:
             h = C.c_void_p()
             nat.check(self._lib.merlin_env_create(C.byref(cfg), C.byref(h)), "merlin_env_create")
         self._h = h
+        self.class_ids = torch.full((self.num_envs,), nat.DIFFICULTY_IDS[uniform], dtype=torch.uint8,
+                                    device=self.device)
+        # True once classes are assigned: the kernels then read the context's class buffer instead of the uniform id
+        # (launches captured into a graph before that keep reading the uniform id)
+        self.per_env_classes = False
+        self.uniform_difficulty = uniform
+        if names is not None:
+            self.set_difficulties(names)
         self._seed_pending = seed
         self._seeded_once = False
         if seeds is not None:
@@ -151,6 +167,45 @@ class MerlinVecEnv:
             nat.check(self._lib.merlin_env_seed(self._h, seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
                                                 self.num_envs, self._stream), "merlin_env_seed")
         self._seeded_once = True
+
+    def _check_names(self, names) -> list:
+        names = [str(d) for d in names]
+        if len(names) != self.num_envs:
+            raise ValueError(f"difficulty: {len(names)} names for {self.num_envs} envs")
+        for d in names:
+            if d not in nat.DIFFICULTY_IDS:
+                raise ValueError(f"Unknown difficulty: {d}")
+        return names
+
+    def set_difficulties(self, names) -> None:
+        """Env i generates its maps with names[i] from its next map generation on (merlin_env_set_difficulties): the
+        envs keep their current maps and RNG streams, every look-ahead map is dropped.  The classes live in one
+        device buffer of the context, so step / reset launches captured into a graph after the first call read a later
+        call's classes without a re-capture.  None restores the constructor's uniform difficulty (and unbinds the
+        buffer).  Syncs the current stream."""
+        if names is None:
+            with torch.cuda.device(self.device):
+                nat.check(self._lib.merlin_env_set_difficulties(self._h, None, 0, self._stream),
+                          "merlin_env_set_difficulties")
+            self.per_env_classes = False
+            self.difficulty, self.difficulties = self.uniform_difficulty, [self.uniform_difficulty] * self.num_envs
+            self.class_ids.fill_(nat.DIFFICULTY_IDS[self.uniform_difficulty])
+            return
+        names = self._check_names(names)
+        self.set_class_ids(np.array([nat.DIFFICULTY_IDS[d] for d in names], dtype=np.int32))
+
+    def set_class_ids(self, ids) -> None:
+        """set_difficulties by MERLIN_* id (int32[num_envs]); the library validates the ids."""
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32))
+        with torch.cuda.device(self.device):
+            nat.check(self._lib.merlin_env_set_difficulties(self._h, ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                            int(ids.size), self._stream),
+                      "merlin_env_set_difficulties")
+        inv = {v: k for k, v in nat.DIFFICULTY_IDS.items()}
+        self.difficulties = [inv[int(v)] for v in ids]
+        self.difficulty = self.difficulties[0] if len(set(self.difficulties)) == 1 else "mixed"
+        self.class_ids.copy_(torch.from_numpy(ids.astype(np.uint8)))
+        self.per_env_classes = True
 
     def reset(self, seed: int | None = None, mask: torch.Tensor | None = None, out: torch.Tensor | None = None):
         """Reset all envs (or those with mask != 0).  Returns the obs codes int32[N, 8]."""

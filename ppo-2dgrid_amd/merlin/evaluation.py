@@ -34,16 +34,27 @@ from .envs import MerlinVecEnv
 SWEEP_SEED_BASE = 200000  # src/sweep_checkpoints.py:79
 
 
+def _per_seed(difficulty, n: int):
+    """`difficulty` as the env takes it: the name, or the per-seed names as a list of n."""
+    if isinstance(difficulty, str):
+        return difficulty
+    names = [str(d) for d in difficulty]
+    if len(names) != n:
+        raise ValueError(f"difficulty: {len(names)} names for {n} seeds")
+    return names
+
+
 @torch.no_grad()
-def evaluate_seeds(ac, seeds, difficulty: str = "mediumhard", size: int = 16, device="cuda",
+def evaluate_seeds(ac, seeds, difficulty="mediumhard", size: int = 16, device="cuda",
                    max_steps: int | None = None, record: bool = False, **env_flags):
     """One deterministic episode per seed, all at once -> (rewards list[float], steps list[int])
-    [+ actions int64[T, n] when record: the actions taken, for replay checks]."""
+    [+ actions int64[T, n] when record: the actions taken, for replay checks].  `difficulty`: one name, or one name
+    per seed (a mixed-task vector env: seed i's map comes from difficulty[i]'s generator)."""
     from .actor_critic import MLPActorCritic
 
     seeds = [int(s) for s in seeds]
     n = len(seeds)
-    env = MerlinVecEnv(n, difficulty=difficulty, size=size, device=device, max_steps=max_steps, seeds=seeds,
+    env = MerlinVecEnv(n, difficulty=_per_seed(difficulty, n), size=size, device=device, max_steps=max_steps, seeds=seeds,
                        **env_flags)
     # an MLP policy (observation.flatten) takes the flattened view its input width names: the RGB partial view
     # (9,408) or the encoded full grid (size * size * 3, observation.fully_observable)
@@ -84,15 +95,15 @@ def evaluate_seeds(ac, seeds, difficulty: str = "mediumhard", size: int = 16, de
 
 
 @torch.no_grad()
-def evaluate_zero_shot(ac, seeds, difficulty: str = "mediumhard", size: int = 16, device="cuda",
+def evaluate_zero_shot(ac, seeds, difficulty="mediumhard", size: int = 16, device="cuda",
                        max_steps: int | None = None, gamma: float = 0.995, lam: float = 0.95, **env_flags):
     """(rewards list[float], steps list[int], losses list[float]), one deterministic episode per
-    seed, all at once (see the module docstring)."""
+    seed, all at once (see the module docstring).  `difficulty`: one name, or one name per seed."""
     from . import _native as nat
 
     seeds = [int(s) for s in seeds]
     n = len(seeds)
-    env = MerlinVecEnv(n, difficulty=difficulty, size=size, device=device, max_steps=max_steps, seeds=seeds,
+    env = MerlinVecEnv(n, difficulty=_per_seed(difficulty, n), size=size, device=device, max_steps=max_steps, seeds=seeds,
                        **env_flags)
     try:
         obs = env.reset().clone()
@@ -144,40 +155,74 @@ def evaluate_zero_shot(ac, seeds, difficulty: str = "mediumhard", size: int = 16
 
 
 def evaluate_few_shot(ac, seeds, adapt_steps: int, lr_inner: float = 0.01, k_support: int = 256,
-                      difficulty: str = "mediumhard", size: int = 16, device="cuda", max_steps: int | None = None,
+                      difficulty="mediumhard", size: int = 16, device="cuda", max_steps: int | None = None,
                       task_batch: int = 32, **env_flags):
     """(rewards list[float], steps list[int], losses list[float]) of src/distribution_over_tasks.py:132-209 for
     many seeds: per seed, a copy of ``ac`` takes ``adapt_steps`` clipped SGD(lr_inner) steps, each on a fresh support
     rollout of ``k_support`` sampled steps of that seed's map, then plays one deterministic episode
     (merlin.few_shot.FewShotAdapter).  The seeds are processed ``task_batch`` at a time, the last chunk padded by
     repeating its last seed (its padded results dropped), so one rollout shape -- one HIP graph -- serves every chunk.
-    adapt_steps = 0 scores ``ac`` itself, as evaluate_zero_shot does.
+    adapt_steps = 0 scores ``ac`` itself, as evaluate_zero_shot does.  `difficulty`: one name, or one name per seed
+    (the padding of the last chunk repeats the last seed's difficulty with it).
 
     The support rollouts' draws are keyed by a seed taken from torch's generator when this function starts, the
     rollout counter, the step and the task's position in its chunk: the same torch.manual_seed and the same calls
     give identical results, and moving a seed to another position (another task_batch) changes its draws."""
+    from . import _native as nat
     from .few_shot import FewShotAdapter
 
     seeds = [int(s) for s in seeds]
+    names = _per_seed(difficulty, len(seeds))
     rewards, steps, losses = [], [], []
     if not seeds:
         return rewards, steps, losses
     B = max(1, min(int(task_batch), len(seeds)))
-    ad = FewShotAdapter(ac, lr_inner=lr_inner, difficulty=difficulty, size=size, device=device, max_steps=max_steps,
+    if isinstance(names, str):
+        base, names = names, None
+    else:  # the task envs are created on the lowest class listed; every chunk then sets its own classes
+        for d in names:
+            if d not in nat.DIFFICULTY_IDS:
+                raise ValueError(f"Unknown difficulty: {d}")
+        base = min(names, key=nat.DIFFICULTY_IDS.__getitem__)
+    ad = FewShotAdapter(ac, lr_inner=lr_inner, difficulty=base, size=size, device=device, max_steps=max_steps,
                         **env_flags)
     try:
         for c0 in range(0, len(seeds), B):
             chunk = seeds[c0:c0 + B]
             m = len(chunk)
             chunk = chunk + [chunk[-1]] * (B - m)
-            params = ad.adapt(chunk, int(adapt_steps), int(k_support))
-            r, s, ls = ad.episode(params, chunk)
+            cls = None if names is None else names[c0:c0 + B] + [names[c0 + m - 1]] * (B - m)
+            params = ad.adapt(chunk, int(adapt_steps), int(k_support), task_difficulties=cls)
+            r, s, ls = ad.episode(params, chunk, task_difficulties=cls)
             rewards += r[:m]
             steps += s[:m]
             losses += ls[:m]
     finally:
         ad.close()
     return rewards, steps, losses
+
+
+def evaluate_across_difficulties(ac, difficulties, num_tasks: int = 50, base_seed: int = 300000, adapt_steps: int = 0,
+                                 **kw) -> dict:
+    """{name: (rewards, steps, losses)} for each of `difficulties`, every one on the same seeds base_seed + i, i <
+    num_tasks (the reference's cross-difficulty analyses: ppo/analyze_ppo_distribution.py collect_zero_shot_metrics,
+    fomaml/analyze_fomaml_distribution.py collect_meta_metrics), in ONE batched pass over len(difficulties) *
+    num_tasks envs of a mixed-task vector env instead of one pass per difficulty.  adapt_steps = 0: zero-shot
+    (evaluate_zero_shot); > 0: after few-shot adaptation (evaluate_few_shot; lr_inner, k_support, task_batch in kw).
+    The envs are laid out difficulty by difficulty, so num_tasks a multiple of 64 keeps every wave on one generator."""
+    names = [str(d) for d in difficulties]
+    if len(set(names)) != len(names):
+        raise ValueError(f"a difficulty is listed twice: {names}")
+    num_tasks = int(num_tasks)
+    seeds = [int(base_seed) + i for i in range(num_tasks)] * len(names)
+    per_seed = [d for d in names for _ in range(num_tasks)]
+    if int(adapt_steps) > 0:
+        res = evaluate_few_shot(ac, seeds, int(adapt_steps), difficulty=per_seed, **kw)
+    else:
+        for k in ("lr_inner", "k_support", "task_batch"):  # few-shot only
+            kw.pop(k, None)
+        res = evaluate_zero_shot(ac, seeds, difficulty=per_seed, **kw)
+    return {d: tuple(x[j * num_tasks:(j + 1) * num_tasks] for x in res) for j, d in enumerate(names)}
 
 
 def evaluate_policy(ac, difficulty: str = "mediumhard", episodes: int = 3, seed: int | None = None,

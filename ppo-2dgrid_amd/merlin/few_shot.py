@@ -79,14 +79,16 @@ class FewShotAdapter:
         nat.group_clip_sgd(new, [g.contiguous() for g in grads], lr, MAX_GRAD_NORM)
         return dict(zip(self.names, new))
 
-    def adapt(self, task_seeds, adapt_steps: int, k_support: int) -> dict:
+    def adapt(self, task_seeds, adapt_steps: int, k_support: int, task_difficulties=None) -> dict:
         """adapt_steps x (support rollout of k_support sampled steps of every task with its current weights, then
-        adapt_step).  adapt_steps = 0: the meta stacks."""
+        adapt_step).  adapt_steps = 0: the meta stacks.  task_difficulties: one difficulty name per task (None: the
+        adapter's difficulty for all); the rollout graphs read the classes from the env's class buffer, so changing
+        them between calls needs no re-capture (FOMAML._task_env)."""
         G = len(task_seeds)
         params = self.meta_params(G)
         if adapt_steps <= 0:
             return params
-        env = self.fm._task_env(task_seeds)
+        env = self.fm._task_env(task_seeds, task_difficulties)
         # the rollout state is looked up by the key alone: the key carries the shape, and a graph recorded on an env
         # that has since been replaced (another G in between) is dropped
         key = f"fs{G}x{int(k_support)}"
@@ -100,13 +102,14 @@ class FewShotAdapter:
         return params
 
     @torch.no_grad()
-    def episode(self, params, task_seeds, max_steps: int | None = None, record: bool = False):
+    def episode(self, params, task_seeds, max_steps: int | None = None, record: bool = False,
+                task_difficulties=None):
         """One deterministic episode per task with its own weights -> (rewards list[float], steps list[int], losses
         list[float]) [+ actions int64 [T, G] on the host when record].  A task's result is frozen at its first done
         (the env then replays the same map; those steps are ignored); a task still running after max_steps (default
-        and at most the env's) counts its steps and rewards so far."""
+        and at most the env's) counts its steps and rewards so far.  task_difficulties: as adapt."""
         G = len(task_seeds)
-        env = self.fm._task_env(task_seeds)
+        env = self.fm._task_env(task_seeds, task_difficulties)
         cap = env.max_steps if not max_steps else min(int(max_steps), env.max_steps)
         dev = self.device
         pk = gp.pack(params)

@@ -73,7 +73,7 @@ class FOMAML:
         self._act_epoch = torch.zeros(1, dtype=torch.int64, device=self.device)
 
     # ------------------------------------------------------------------ envs
-    def _task_env(self, task_seeds) -> MerlinVecEnv:
+    def _task_env(self, task_seeds, task_difficulties=None) -> MerlinVecEnv:
         G = len(task_seeds)
         if self._env is None or self._env.num_envs != G:
             if self._env is not None:
@@ -81,15 +81,26 @@ class FOMAML:
             self._env = MerlinVecEnv(G, device=self.device, reseed_each_reset=True, **self.env_kwargs)
         self._task_seeds = np.asarray(task_seeds, dtype=np.uint64)
         self._env.seed_each(self._task_seeds)
+        # per-task generators (one env per task).  The env kernels read the classes from the context's class buffer,
+        # whose address never changes, so the captured rollout graphs below see each meta batch's classes without a
+        # re-capture.  A graph captured while the env was still uniform reads no buffer: _rollout_state drops it on
+        # the first per-task assignment; after that, None assigns the uniform class through the same buffer.
+        if task_difficulties is not None:
+            self._env.set_difficulties(task_difficulties)
+        elif self._env.per_env_classes:
+            self._env.set_difficulties([self._env.uniform_difficulty] * G)
         return self._env
 
     # ------------------------------------------------------------ rollouts
     def _rollout_state(self, key, G, steps, params):
         st = self._rollouts.get(key)
+        per_env = bool(self._env is not None and self._env.per_env_classes)
         if st is not None and st["G"] == G and st["steps"] == steps:
+            if st["per_env"] != per_env:  # recorded before the env read its class buffer: record again, same storage
+                st["graph"], st["per_env"] = None, per_env
             return st
         dev = self.device
-        st = {"G": G, "steps": steps, "graph": None,
+        st = {"G": G, "steps": steps, "graph": None, "per_env": per_env,
               "codes": torch.zeros((steps + 1, G, 8), dtype=torch.int32, device=dev),
               "act": torch.zeros((steps, G), dtype=torch.int64, device=dev),
               "logp": torch.zeros((steps, G), dtype=torch.float32, device=dev),
@@ -258,9 +269,10 @@ class FOMAML:
         g.replay()  # the capture recorded the launches without running them
         return out
 
-    def meta_train_step(self, task_seeds, k_support=50, k_query=50):
+    def meta_train_step(self, task_seeds, k_support=50, k_query=50, task_difficulties=None):
+        """task_difficulties: one difficulty name per task (None: every task is of this object's difficulty)."""
         G = len(task_seeds)
-        env = self._task_env(task_seeds)
+        env = self._task_env(task_seeds, task_difficulties)
         names = [n for n, _ in self.meta_policy.named_parameters()]
         st = self._steps.setdefault((G, k_support, k_query), {"eager": 0})
         if "outer" not in st:

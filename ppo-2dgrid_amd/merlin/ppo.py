@@ -338,6 +338,35 @@ class PPO:
         self.episode_returns.extend(rets.cpu().tolist())
         self.episode_lengths.extend(int(x) for x in lens.cpu().tolist())
 
+    def episode_class_stats(self, out=None, accumulate=False) -> torch.Tensor:
+        """float64 [5, 4] on the device: per difficulty id (episodes, sum return, sum return^2, sum length) of the
+        episodes that finished in the last rollout (merlin_episode_class_stats: two launches, no host sync).  Under
+        data parallelism this is the rank's shard; the rows are plain sums, so the caller adds them across ranks
+        (all_reduce SUM) before taking means."""
+        if self.vec is None:
+            raise ValueError("per-difficulty episode statistics need the vector env")
+        buf = self.buf
+        return nat.episode_class_stats(buf.dones, buf.ep_return, buf.ep_length, self.vec.class_ids,
+                                       len(nat.DIFFICULTY_IDS), out=out, accumulate=accumulate)
+
+    def episode_stats_by_difficulty(self) -> dict:
+        """{difficulty: (episodes, mean return, std return, mean length)} of the last rollout's finished episodes,
+        for the difficulties the env holds (population std; a difficulty with no finished episode reports
+        (0, nan, nan, nan)).  One [5, 4] device-to-host copy.  Under data parallelism each rank reports its own
+        shard: sum episode_class_stats() across ranks for the global figures."""
+        rows = self.episode_class_stats().cpu().tolist()
+        out = {}
+        for name, cid in nat.DIFFICULTY_IDS.items():
+            if name not in self.vec.difficulties:
+                continue
+            n, s1, s2, sl = rows[cid]
+            if n > 0:
+                mean = s1 / n
+                out[name] = (int(n), mean, max(s2 / n - mean * mean, 0.0) ** 0.5, sl / n)
+            else:
+                out[name] = (0, float("nan"), float("nan"), float("nan"))
+        return out
+
     def _collect_rollouts_single(self):
         """Reference loop (ppo.py:64-105) for a generic gym env."""
         state, _ = self.env.reset()

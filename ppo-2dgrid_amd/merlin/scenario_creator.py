@@ -17,6 +17,7 @@ import os
 
 import yaml
 
+from . import task_mix
 from .envs import MerlinEnv, MerlinVecEnv
 
 DEFAULT_CONFIG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "config", "scenario.yaml")
@@ -58,6 +59,25 @@ class ScenarioCreator:
         gen = _ENV_IDS.get(cfg["env_id"], difficulty)
         return {"difficulty": gen, "size": int(kw.pop("size", 16)), **kw}
 
+    def _mix_env_kwargs(self, mix, num_envs: int, align: int = 64) -> dict:
+        """_env_kwargs of a mixture of the config's difficulties ({name: weight} or "name:w,..."): `difficulty` is
+        the per-env generator list of task_mix.assign.  The difficulties may differ in their generator only: one
+        vector env has one grid size and one set of params (the reference rejects mixed sizes too,
+        _validate_grid_sizes)."""
+        weights = task_mix.parse_mix(mix)
+        by_gen, common, first = {}, None, None
+        for name, w in weights.items():
+            kw = self._env_kwargs(name)
+            gen = kw.pop("difficulty")
+            if common is None:
+                common, first = kw, name
+            elif kw != common:
+                diff = sorted(k for k in set(kw) | set(common) if kw.get(k) != common.get(k))
+                raise ValueError(f"difficulties {first} and {name} differ in {diff}: one vector env has one size and "
+                                 "one set of params")
+            by_gen[gen] = by_gen.get(gen, 0.0) + w
+        return {"difficulty": task_mix.assign(num_envs, by_gen, align=align), **common}
+
     def create_env(self, difficulty: str = "easy", seed=None, device="cuda", **flags):
         """The single env of scenario_creator.py:35-57 with the configured observation wrappers (observation.
         fully_observable: the encoded full grid instead of the RGB partial view; observation.flatten: as a vector)."""
@@ -65,19 +85,21 @@ class ScenarioCreator:
                "flatten": bool(self.obs_cfg.get("flatten", False))}
         return MerlinEnv(device=device, **self._env_kwargs(difficulty), **obs, **flags)
 
-    def create_vec_env(self, difficulty: str, num_envs: int, seed=None, device="cuda", env_offset: int = 0,
+    def create_vec_env(self, difficulty, num_envs: int, seed=None, device="cuda", env_offset: int = 0,
                        **flags) -> MerlinVecEnv:
         """N envs for the batched trainer.  Their step produces the RGB partial view's tile codes; with
         observation.flatten the batched trainer takes the reference's MLP path on the flattened view (the RGB view, or
         with observation.fully_observable the encoded full grid: MerlinVecEnv.flat_obs / render_full).  The full grid
         unflattened is refused: it is 16 x 16, smaller than CNNActorCritic's receptive field (the reference's CNN
-        fails on it too)."""
+        fails on it too).  `difficulty` is one of the config's names, or a mixture of them ({name: weight} or
+        "name:w,..."): the envs are then split among the difficulties by merlin.task_mix.assign."""
         full, flat = bool(self.obs_cfg.get("fully_observable", False)), bool(self.obs_cfg.get("flatten", False))
         if full and not flat:
             raise ValueError("CNNActorCritic trains on the (56, 56, 3) RGB partial view (src/actor_critic.py:22-28); "
                              "observation.fully_observable without flatten gives a grid smaller than its receptive field")
+        kw = self._mix_env_kwargs(difficulty, num_envs) if task_mix.is_mix(difficulty) else self._env_kwargs(difficulty)
         return MerlinVecEnv(num_envs, seed=seed, device=device, env_offset=env_offset, fully_observable=full,
-                            flatten=flat, **self._env_kwargs(difficulty), **flags)
+                            flatten=flat, **kw, **flags)
 
     def sample_scenarios(self, n: int = 5, difficulty: str = "easy"):
         return [self.create_env(difficulty) for _ in range(n)]

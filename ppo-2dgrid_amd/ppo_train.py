@@ -10,6 +10,11 @@ Same flags and defaults as the reference, plus:
   --size S          grid side override (default: scenario.yaml, 16)
   --stuck_penalty / --exploration_bonus [--bonus B]   reward-shaping flags (off by default)
   --config PATH     scenario YAML (default: the packaged copy of src/config/scenario.yaml)
+  --difficulty_mix "name:w,..."   train on a mixture of difficulties (needs --num_envs > 1): the envs are split among
+                    them by weight in wave-aligned runs (merlin.task_mix.assign); every iteration also prints the
+                    per-difficulty mean return / length of the rollout's finished episodes and logs them under
+                    train_by_difficulty/<name>/.  Evaluation, the run's name and the checkpoints still follow
+                    --difficulty.
 Outputs keep the reference's layout: checkpoints/<env_id>_<WxH>_<difficulty>_<ts>/seed_<s>/
 {best_model, ppo_model_<k>k, ppo_model_final}.pth (CNNActorCritic state_dicts with the
 reference's keys) and tb_logs/... scalars (TensorBoard when installed, else scalars.jsonl).
@@ -31,6 +36,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from merlin import PPO, ScenarioCreator  # noqa: E402
+from merlin._native import DIFFICULTY_IDS  # noqa: E402
 from merlin.distributed import DataParallel  # noqa: E402
 from merlin.evaluation import evaluate_policy  # noqa: E402
 from merlin.metrics.ppo_metrics import compute_episode_stats  # noqa: E402
@@ -69,6 +75,7 @@ def parse_args(argv=None):
     p.add_argument("--exploration_bonus", action="store_true")
     p.add_argument("--bonus", type=float, default=0.01)
     p.add_argument("--config", type=str, default=DEFAULT_CONFIG)
+    p.add_argument("--difficulty_mix", type=str, default=None, help='e.g. "easy:1,mediumhard:2,hard:1"')
     return p.parse_args(argv)
 
 
@@ -141,8 +148,10 @@ def train_minigrid(args):
     flags = dict(stuck_penalty=args.stuck_penalty, exploration_bonus=args.exploration_bonus, bonus=args.bonus)
     size_kw = {} if args.size is None else {"size": args.size}
     batch = args.num_envs * args.k_steps if args.k_steps else args.batch_size
+    if args.difficulty_mix and args.num_envs <= 1:
+        raise SystemExit("--difficulty_mix splits a vector env among difficulties: it needs --num_envs > 1")
     if args.num_envs > 1:
-        env = sc.create_vec_env(args.difficulty, args.num_envs, seed=args.seed, device=device,
+        env = sc.create_vec_env(args.difficulty_mix or args.difficulty, args.num_envs, seed=args.seed, device=device,
                                 env_offset=rank * args.num_envs, **size_kw, **flags)
     else:
         # rank r's single env is global env r: seed + r, and its action draws are keyed by r
@@ -172,6 +181,13 @@ def train_minigrid(args):
     while step_count < args.total_steps:
         t0 = time.time()
         last_value = agent.collect_rollouts()
+        # the rollout's finished episodes by difficulty, before update() (the rows are this rank's shard: summed
+        # across ranks, every rank taking part, so the lead logs the global figures)
+        by_diff = None
+        if args.difficulty_mix:
+            rows = agent.episode_class_stats()
+            dp.allreduce_sum_(rows)
+            by_diff = {d: rows[c].tolist() for d, c in DIFFICULTY_IDS.items() if d in env.difficulties}
         update_stats = agent.update(last_value)
         step_count += steps_per_iter
         sps = steps_per_iter / (time.time() - t0)
@@ -193,6 +209,17 @@ def train_minigrid(args):
                          ("diagnostics/gradnorm", "gradnorm")):
             writer.add_scalar(tag, update_stats[key], step_count)
         writer.add_scalar("perf/env_steps_per_sec", sps, step_count)
+        if by_diff:
+            parts = []
+            for d, (n, s1, _, sl) in by_diff.items():
+                writer.add_scalar(f"train_by_difficulty/{d}/episodes", n, step_count)
+                if n > 0:
+                    writer.add_scalar(f"train_by_difficulty/{d}/episode_return_mean", s1 / n, step_count)
+                    writer.add_scalar(f"train_by_difficulty/{d}/episode_length_mean", sl / n, step_count)
+                    parts.append(f"{d}: R {s1 / n:.3f} len {sl / n:.1f} ({int(n)} ep)")
+                else:
+                    parts.append(f"{d}: no episode")
+            print(f"[{step_count:>7}] by difficulty | " + " | ".join(parts), flush=True)
         if agent.episode_returns:
             st = compute_episode_stats(agent.episode_returns[-10:], agent.episode_lengths[-10:])
             writer.add_scalar("stats/episode_return_mean", st["episode_return_mean"], step_count)
