@@ -100,6 +100,10 @@ extern "C" {
 #define MERLIN_DEVERR_SLOT_EMPTY 8u  /* a reset met an empty look-ahead slot with the step fallback off */
 #define MERLIN_DEVERR_BAD_TILE 4u    /* merlin_tower_codes_conv3: a frame that is no observation (the agent tile (class
                                       * 4) missing at view cell (3, 6) or present elsewhere): merlin_tower_errors */
+#define MERLIN_DEVERR_BAD_FRAME 16u  /* a rendered frame's agent was outside the grid, on a wall or had a direction
+                                      * outside 0..3, or its env id was out of range: the frame is drawn without the
+                                      * agent and its highlight.  merlin_env_render: merlin_env_errors;
+                                      * merlin_render_frames: merlin_tower_errors */
 
 /* observation layouts for merlin_obs_expand_f32 */
 #define MERLIN_LAYOUT_NCHW 0 /* [n][3][56][56]: what CNNActorCritic._format_obs hands the convs */
@@ -231,6 +235,36 @@ int merlin_env_full_obs(merlin_env *env, uint8_t *out_dev, void *stream);
  * Any pointer may be NULL. */
 int merlin_env_get_state(merlin_env *env, uint32_t *walls_host, int32_t *agent_host,
                          uint64_t *rng_host, void *stream);
+/* Full-grid RGB frames: minigrid's render() in rgb_array mode, get_frame(highlight, tile_size) -- the whole grid at
+ * tile_size-pixel tiles (4..32; minigrid's default 32), tile (i, j) at img[ts*j : ts*j+ts, ts*i : ts*i+ts], the agent's
+ * triangle in its world direction, every cell the agent's 7x7 view shows brightened when highlight != 0.
+ * The frame atlas holds the MERLIN_FRAME_TILES = 22 tiles a frame is made of, per tile size, in this order:
+ *   0..5    object + 3 * highlighted, object 0 empty / 1 wall / 2 goal, no agent
+ *   6..21   6 + ((on_goal * 4 + agent_dir) * 2 + highlighted): the agent on an empty cell (on_goal 0) or on the goal
+ *           (1: the terminal state when the caller does not auto-reset), agent_dir 0..3
+ * built on first use by the library's restatement of minigrid's render_tile and cached, on the host and per device
+ * (the first render of a tile size on a device uploads it: not capturable; later ones are). */
+#define MERLIN_FRAME_TILES 22
+/* [host] out_host uint8[22][tile_size][tile_size][3]; tile_size outside 4..32: MERLIN_E_INVALID */
+int merlin_frame_atlas(int32_t tile_size, uint8_t *out_host);
+/* Stateless: frame f < n_frames shows map m = map_index_dev[f] (NULL: f) -- walls_dev uint32[M][size] bit rows as
+ * merlin_env_get_state defines them, goal_dev int32[M][2] = (x, y) (NULL or a position outside the grid: no goal) --
+ * with the agent agent_dev[f] int32[4] = (x, y, dir, 0).  out_dev uint8[n_frames][size*ts][size*ts][3]; any
+ * alignment.  size outside 5..32, tile_size outside 4..32, negative n_frames or a null pointer: MERLIN_E_INVALID.
+ * An agent outside the grid, on a wall or with dir outside 0..3 indexes nothing: its frame is drawn without the
+ * agent and MERLIN_DEVERR_BAD_FRAME is raised (merlin_tower_errors).  map_index_dev's values are the caller's to
+ * keep inside [0, M): the entry is not told M. */
+int merlin_render_frames(const uint32_t *walls_dev, const int32_t *goal_dev, const int32_t *agent_dev,
+                         const int32_t *map_index_dev, int64_t n_frames, int32_t size, int32_t tile_size,
+                         int32_t highlight, uint8_t *out_dev, void *stream);
+/* The same kernel on the context's own current state: frame k < n shows env index_dev[k] (int64 env ids; NULL:
+ * env k, and n must be num_envs).  An env id outside [0, num_envs): MERLIN_DEVERR_BAD_FRAME (merlin_env_errors). */
+int merlin_env_render(merlin_env *env, const int64_t *index_dev, int64_t n, int32_t tile_size,
+                      int32_t highlight, uint8_t *out_dev, void *stream);
+/* Device-to-device copy of the current state in merlin_render_frames' layouts: walls_dev uint32[N][size], goal_dev
+ * int32[N][2], agent_dev int32[N][4].  Any pointer may be NULL.  One kernel, no host sync: capturable. */
+int merlin_env_snapshot(merlin_env *env, uint32_t *walls_dev, int32_t *goal_dev, int32_t *agent_dev,
+                        void *stream);
 /* [sync] read-and-clear the device error bits and the fallback-map counter. */
 int merlin_env_errors(merlin_env *env, uint32_t *flags_host, uint32_t *fallbacks_host,
                       void *stream);

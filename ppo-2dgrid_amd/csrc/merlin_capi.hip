@@ -6,6 +6,7 @@
 
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include <algorithm>
 
@@ -142,14 +143,16 @@ struct Tri {
     }
 };
 
-void render_tile(int obj /*0 none 1 wall 2 goal*/, bool agent, bool highlight, uint8_t out[8][8][3]) {
-    static uint8_t img[24][24][3];
-    memset(img, 0, sizeof(img));
-    auto fill_rect = [](double xmin, double xmax, double ymin, double ymax, const uint8_t col[3]) {
-        for (int y = 0; y < 24; y++)
-            for (int x = 0; x < 24; x++) {
-                const double yf = (y + 0.5) / 24, xf = (x + 0.5) / 24;
-                if (xf >= xmin && xf <= xmax && yf >= ymin && yf <= ymax) memcpy(img[y][x], col, 3);
+// agent_dir < 0: no agent; out uint8[ts][ts][3]
+void render_tile(int obj /*0 none 1 wall 2 goal*/, int agent_dir, bool highlight, int ts, uint8_t *out) {
+    const int N = 3 * ts;  // subdivs = 3
+    std::vector<uint8_t> canvas((size_t)N * N * 3, 0);
+    auto img = [&](int y, int x) { return canvas.data() + ((size_t)y * N + x) * 3; };
+    auto fill_rect = [&](double xmin, double xmax, double ymin, double ymax, const uint8_t col[3]) {
+        for (int y = 0; y < N; y++)
+            for (int x = 0; x < N; x++) {
+                const double yf = (y + 0.5) / N, xf = (x + 0.5) / N;
+                if (xf >= xmin && xf <= xmax && yf >= ymin && yf <= ymax) memcpy(img(y, x), col, 3);
             }
     };
     const uint8_t grey[3] = {100, 100, 100}, green[3] = {0, 255, 0}, red[3] = {255, 0, 0};
@@ -157,37 +160,35 @@ void render_tile(int obj /*0 none 1 wall 2 goal*/, bool agent, bool highlight, u
     fill_rect(0, 1, 0, 0.031, grey);
     if (obj == 1) fill_rect(0, 1, 0, 1, grey);
     if (obj == 2) fill_rect(0, 1, 0, 1, green);
-    if (agent) {
+    if (agent_dir >= 0) {
         const Tri tri;
-        const double theta = 0.5 * M_PI * 3;  // agent_dir = 3 in get_pov_render
+        const double theta = 0.5 * M_PI * agent_dir;  // rotate_fn(tri, cx=0.5, cy=0.5, theta=0.5*pi*agent_dir)
         const double c = cos(-theta), s = sin(-theta);
-        for (int y = 0; y < 24; y++)
-            for (int x = 0; x < 24; x++) {
-                const double yf = (y + 0.5) / 24, xf = (x + 0.5) / 24;
+        for (int y = 0; y < N; y++)
+            for (int x = 0; x < N; x++) {
+                const double yf = (y + 0.5) / N, xf = (x + 0.5) / N;
                 const double px = xf - 0.5, py = yf - 0.5;
                 const double x2 = (0.5 + px * c) - py * s;
                 const double y2 = (0.5 + py * c) + px * s;
-                if (tri.in(x2, y2)) memcpy(img[y][x], red, 3);
+                if (tri.in(x2, y2)) memcpy(img(y, x), red, 3);
             }
     }
     if (highlight)
-        for (int y = 0; y < 24; y++)
-            for (int x = 0; x < 24; x++)
-                for (int k = 0; k < 3; k++) {
-                    const uint8_t p = img[y][x][k];
-                    double v = (double)p + 0.30 * (double)(uint8_t)(255 - p);
-                    v = v < 0 ? 0 : (v > 255 ? 255 : v);
-                    img[y][x][k] = (uint8_t)v;
-                }
-    for (int Y = 0; Y < 8; Y++)
-        for (int X = 0; X < 8; X++)
+        for (uint8_t &px : canvas) {
+            const uint8_t p = px;
+            double v = (double)p + 0.30 * (double)(uint8_t)(255 - p);
+            v = v < 0 ? 0 : (v > 255 ? 255 : v);
+            px = (uint8_t)v;
+        }
+    for (int Y = 0; Y < ts; Y++)
+        for (int X = 0; X < ts; X++)
             for (int k = 0; k < 3; k++) {
                 double m[3];
                 for (int sy = 0; sy < 3; sy++) {
-                    const uint8_t *r0 = img[3 * Y + sy][3 * X];
+                    const uint8_t *r0 = img(3 * Y + sy, 3 * X);
                     m[sy] = (((double)r0[k] + (double)r0[3 + k]) + (double)r0[6 + k]) / 3.0;
                 }
-                out[Y][X][k] = (uint8_t)(((m[0] + m[1]) + m[2]) / 3.0);
+                out[(Y * ts + X) * 3 + k] = (uint8_t)(((m[0] + m[1]) + m[2]) / 3.0);
             }
 }
 
@@ -196,12 +197,35 @@ std::once_flag g_atlas_once;
 
 void build_atlas() {
     std::call_once(g_atlas_once, [] {
-        render_tile(0, false, false, g_atlas[0]);  // not visible: empty, no highlight
-        render_tile(0, false, true, g_atlas[1]);   // visible empty
-        render_tile(1, false, true, g_atlas[2]);   // visible wall
-        render_tile(2, false, true, g_atlas[3]);   // visible goal
-        render_tile(0, true, true, g_atlas[4]);    // agent (view cell (3,6), agent_dir 3)
+        render_tile(0, -1, false, 8, &g_atlas[0][0][0][0]);  // not visible: empty, no highlight
+        render_tile(0, -1, true, 8, &g_atlas[1][0][0][0]);   // visible empty
+        render_tile(1, -1, true, 8, &g_atlas[2][0][0][0]);   // visible wall
+        render_tile(2, -1, true, 8, &g_atlas[3][0][0][0]);   // visible goal
+        render_tile(0, 3, true, 8, &g_atlas[4][0][0][0]);    // agent (view cell (3,6), agent_dir 3 in get_pov_render)
     });
+}
+
+// the frame atlas of one tile size (include/merlin_hip.h MERLIN_FRAME_TILES, the order fixed there), built on first
+// use and kept
+constexpr int FRAME_TS_MIN = 4, FRAME_TS_MAX = 32;
+std::vector<uint8_t> g_frame_atlas[FRAME_TS_MAX + 1];
+std::mutex g_frame_atlas_mu;
+
+const std::vector<uint8_t> &frame_atlas(int ts) {
+    std::lock_guard<std::mutex> lk(g_frame_atlas_mu);
+    std::vector<uint8_t> &a = g_frame_atlas[ts];
+    if (a.empty()) {
+        const size_t tile = (size_t)ts * ts * 3;
+        a.resize(MERLIN_FRAME_TILES * tile);
+        for (int hl = 0; hl < 2; hl++)
+            for (int obj = 0; obj < 3; obj++) render_tile(obj, -1, hl != 0, ts, a.data() + (obj + 3 * hl) * tile);
+        for (int on_goal = 0; on_goal < 2; on_goal++)
+            for (int dir = 0; dir < 4; dir++)
+                for (int hl = 0; hl < 2; hl++)
+                    render_tile(on_goal ? 2 : 0, dir, hl != 0, ts,
+                                a.data() + (6 + ((on_goal * 4 + dir) * 2 + hl)) * tile);
+    }
+    return a;
 }
 
 // per-device one-time init: atlas upload + GAE partials workspace
@@ -216,6 +240,7 @@ struct DeviceWs {
     double *stage_part = nullptr;  // conv tables' adjoint: the 625-combination type's partial dW2 sums
     uint32_t *tower_err = nullptr;  // device error flags of the tower kernels (merlin_tower_errors)
     double *eps_part = nullptr;     // merlin_episode_class_stats: the per-block class sums
+    uint8_t *frame_atlas[33] = {};  // the frame atlas by tile size (merlin_render.hip), uploaded on first use
 };
 constexpr int MAX_DEV = 64;
 DeviceWs g_dev[MAX_DEV];
@@ -249,6 +274,27 @@ int device_ws(DeviceWs **out) {
     return MERLIN_OK;
 }
 
+// the device copy of the frame atlas of tile size ts (4..32), uploaded at the first render of that size
+int device_frame_atlas(int ts, const uint8_t **out, uint32_t **err) {
+    DeviceWs *ws = nullptr;
+    int rc = device_ws(&ws);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(g_dev_mu);
+    if (!ws->frame_atlas[ts]) {
+        const std::vector<uint8_t> &a = frame_atlas(ts);
+        uint8_t *d = nullptr;
+        HIP_TRY(hipMalloc(&d, a.size()));
+        hipError_t e = hipMemcpy(d, a.data(), a.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            return hip_fail(e, "hipMemcpy(frame atlas)");
+        }
+        ws->frame_atlas[ts] = d;
+    }
+    *out = ws->frame_atlas[ts];
+    if (err) *err = ws->tower_err;
+    return MERLIN_OK;
+}
 
 // zero_async's kernel: a 16-B aligned body by grid-stride uint4 stores; the unaligned head and the tail (< 16 B each)
 // by block 0's first lanes, byte stores
@@ -285,6 +331,54 @@ int merlin_tile_atlas(uint8_t *out_host) {
     if (!out_host) return fail(MERLIN_E_INVALID, "null output");
     build_atlas();
     memcpy(out_host, g_atlas, sizeof(g_atlas));
+    return MERLIN_OK;
+}
+
+int merlin_frame_atlas(int32_t tile_size, uint8_t *out_host) {
+    if (!out_host) return fail(MERLIN_E_INVALID, "null output");
+    if (tile_size < FRAME_TS_MIN || tile_size > FRAME_TS_MAX) return fail(MERLIN_E_INVALID, "tile_size must be in [4, 32]");
+    const std::vector<uint8_t> &a = frame_atlas(tile_size);
+    memcpy(out_host, a.data(), a.size());
+    return MERLIN_OK;
+}
+
+int merlin_render_frames(const uint32_t *walls, const int32_t *goal, const int32_t *agent, const int32_t *map_index,
+                         int64_t n_frames, int32_t size, int32_t tile_size, int32_t highlight, uint8_t *out,
+                         void *stream) {
+    if (size < 5 || size > 32) return fail(MERLIN_E_INVALID, "grid size must be in [5, 32]");
+    if (tile_size < FRAME_TS_MIN || tile_size > FRAME_TS_MAX) return fail(MERLIN_E_INVALID, "tile_size must be in [4, 32]");
+    if (n_frames < 0) return fail(MERLIN_E_INVALID, "negative frame count");
+    if (n_frames == 0) return MERLIN_OK;
+    if (!walls || !agent || !out) return fail(MERLIN_E_INVALID, "null argument");
+    const uint8_t *atlas = nullptr;
+    uint32_t *err = nullptr;
+    int rc = device_frame_atlas(tile_size, &atlas, &err);
+    if (rc) return rc;
+    HIP_TRY(merlin::launch_render_frames(walls, goal, agent, map_index, n_frames, size, tile_size, highlight, atlas,
+                                         out, err, (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_env_render(merlin_env *e, const int64_t *index, int64_t n, int32_t tile_size, int32_t highlight,
+                      uint8_t *out, void *stream) {
+    if (!e) return fail(MERLIN_E_INVALID, "null env");
+    if (!e->has_state) return fail(MERLIN_E_INVALID, "merlin_env_render before merlin_env_reset");
+    if (tile_size < FRAME_TS_MIN || tile_size > FRAME_TS_MAX) return fail(MERLIN_E_INVALID, "tile_size must be in [4, 32]");
+    if (n < 0 || (!index && n != e->dev.n)) return fail(MERLIN_E_INVALID, "without env ids, n must be num_envs");
+    if (n == 0) return MERLIN_OK;
+    if (!out) return fail(MERLIN_E_INVALID, "null output");
+    const uint8_t *atlas = nullptr;
+    int rc = device_frame_atlas(tile_size, &atlas, nullptr);
+    if (rc) return rc;
+    HIP_TRY(merlin::launch_env_render(e->dev, index, n, tile_size, highlight, atlas, out, (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_env_snapshot(merlin_env *e, uint32_t *walls, int32_t *goal, int32_t *agent, void *stream) {
+    if (!e) return fail(MERLIN_E_INVALID, "null env");
+    if (!e->has_state) return fail(MERLIN_E_INVALID, "merlin_env_snapshot before merlin_env_reset");
+    if (!walls && !goal && !agent) return MERLIN_OK;
+    HIP_TRY(merlin::launch_env_snapshot(e->dev, walls, goal, agent, (hipStream_t)stream));
     return MERLIN_OK;
 }
 

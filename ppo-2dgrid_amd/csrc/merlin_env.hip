@@ -461,77 +461,19 @@ __device__ __noinline__ void generate_map(uint32_t (*rows)[NB], int lane, int S,
     generate_map_inl<SP, NB>(rows, lane, S, difficulty, r, fallbacks, o);
 }
 
-__device__ __forceinline__ uint32_t bitrev7(uint32_t v) { return __brev(v) >> 25; }
-
 // gen_obs_grid + get_pov_render tile classes -> 8 packed nibble words.
 template <int SP, int NB>
 __device__ __forceinline__ void view_codes(const uint32_t (*rows)[NB], int lane, int S, int ax, int ay, int dir,
                                            int goal_x, int goal_y, bool goal_set,
                                            uint32_t out[MERLIN_OBS_WORDS]) {
-    // get_view_exts (top-left of the 7x7 world window)
-    int tx, ty;
-    if (dir == 0) {
-        tx = ax;
-        ty = ay - 3;
-    } else if (dir == 1) {
-        tx = ax - 3;
-        ty = ay;
-    } else if (dir == 2) {
-        tx = ax - 6;
-        ty = ay - 3;
-    } else {
-        tx = ax - 3;
-        ty = ay - 6;
-    }
-    // Grid.slice: out-of-bounds cells read as Wall
-    const uint64_t hi_ones = ~0ULL << (S + 8);
-    uint32_t win[7];
-#pragma unroll
-    for (int r = 0; r < 7; r++) {
-        const int y = ty + r;
-        const bool in = (y >= 0) && (y < S);
-        const uint32_t row = in ? rows[in ? y : 0][lane] : 0xffffffffu;
-        const uint64_t w = ((uint64_t)row << 8) | 0xffULL | hi_ones;
-        win[r] = (uint32_t)(w >> (tx + 8)) & 0x7fu;  // bit c = cell (c, r) of the slice
-    }
-    // rotate_left applied k = (dir+1) mod 4 times: built from transpose / row flip / bit reverse
-    uint32_t tr[7];
-#pragma unroll
-    for (int x = 0; x < 7; x++) {
-        uint32_t v = 0u;
-#pragma unroll
-        for (int y = 0; y < 7; y++) v |= ((win[y] >> x) & 1u) << y;
-        tr[x] = v;
-    }
-    const int k = (dir + 1) & 3;
-    const bool odd = k & 1, flip = (k == 1) || (k == 2), rev = (k >= 2);
-    uint32_t V[7];  // V[j] bit i = view cell (i, j) is a wall
-#pragma unroll
-    for (int b = 0; b < 7; b++) {
-        uint32_t m = flip ? (odd ? tr[6 - b] : win[6 - b]) : (odd ? tr[b] : win[b]);
-        V[b] = rev ? bitrev7(m) : m;
-    }
+    uint32_t V[7], m[7];  // window, rotation, occlusion: merlin_internal.h view_mask
+    view_mask([&](int y) { return rows[y][lane]; }, S, ax, ay, dir, V, m);
     // goal position in view: view(vi,vj) <- world(agent + (6-vj)*F + (vi-3)*R)
     const int Fx = (dir == 0) - (dir == 2), Fy = (dir == 1) - (dir == 3);
     const int Rx = -Fy, Ry = Fx;  // DIR_TO_VEC[(dir+1)%4]
     const int dx = goal_x - ax, dy = goal_y - ay;
     const int gvj = 6 - (dx * Fx + dy * Fy), gvi = 3 + (dx * Rx + dy * Ry);
     const bool ginv = goal_set && gvi >= 0 && gvi < 7 && gvj >= 0 && gvj < 7;
-    // Grid.process_vis(agent_pos=(3,6)) as row bit-ops (walls opaque, goal/empty transparent)
-    uint32_t m[7] = {0u, 0u, 0u, 0u, 0u, 0u, 1u << 3};
-#pragma unroll
-    for (int j = 6; j >= 0; j--) {
-        const uint32_t T = ~V[j] & 0x7fu;
-        uint32_t M = m[j];
-#pragma unroll
-        for (int s = 0; s < 6; s++) M |= (M & T & 0x3fu) << 1;  // left-to-right pass
-        const uint32_t e1 = M & T & 0x3fu;
-#pragma unroll
-        for (int s = 0; s < 6; s++) M |= (M & T & 0x7eu) >> 1;  // right-to-left pass
-        const uint32_t e2 = M & T & 0x7eu;
-        m[j] = M;
-        if (j > 0) m[j - 1] |= e1 | (e1 << 1) | e2 | (e2 >> 1);
-    }
 #pragma unroll
     for (int w = 0; w < MERLIN_OBS_WORDS; w++) out[w] = 0u;
 #pragma unroll

@@ -201,6 +201,77 @@ __device__ __forceinline__ int act_from_parts(const ActIn &c, int64_t n, int64_t
     return act_finish(acc, c.ba, c.bc, c.A, c.det, c.seed, ep, c.step, c.env_offset, k, c.action, c.logp, c.value);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The agent's 7x7 view (minigrid gen_obs_grid): the world window in front of the agent, rotated so that the agent
+// sits at view cell (3, 6) facing up, and its visibility mask.  Shared by the observation (merlin_env.hip
+// view_codes) and the full-grid renderer's highlight (merlin_render.hip).  row(y) returns the wall bits of grid row
+// y, 0 <= y < S (bit x = wall at (x, y)).  V[j] bit i = view cell (i, j) is a wall, m[j] bit i = it is visible.
+// View cell (vi, vj) shows world cell agent + (6 - vj) F + (vi - 3) R, F = DIR_TO_VEC[dir], R = DIR_TO_VEC[dir + 1].
+__device__ __forceinline__ uint32_t bitrev7(uint32_t v) { return __brev(v) >> 25; }
+
+template <class RowFn>
+__device__ __forceinline__ void view_mask(RowFn row, int S, int ax, int ay, int dir, uint32_t V[7], uint32_t m[7]) {
+    // get_view_exts (top-left of the 7x7 world window)
+    int tx, ty;
+    if (dir == 0) {
+        tx = ax;
+        ty = ay - 3;
+    } else if (dir == 1) {
+        tx = ax - 3;
+        ty = ay;
+    } else if (dir == 2) {
+        tx = ax - 6;
+        ty = ay - 3;
+    } else {
+        tx = ax - 3;
+        ty = ay - 6;
+    }
+    // Grid.slice: out-of-bounds cells read as Wall
+    const uint64_t hi_ones = ~0ULL << (S + 8);
+    uint32_t win[7];
+#pragma unroll
+    for (int r = 0; r < 7; r++) {
+        const int y = ty + r;
+        const bool in = (y >= 0) && (y < S);
+        const uint32_t bits = in ? row(in ? y : 0) : 0xffffffffu;
+        const uint64_t w = ((uint64_t)bits << 8) | 0xffULL | hi_ones;
+        win[r] = (uint32_t)(w >> (tx + 8)) & 0x7fu;  // bit c = cell (c, r) of the slice
+    }
+    // rotate_left applied k = (dir+1) mod 4 times: built from transpose / row flip / bit reverse
+    uint32_t tr[7];
+#pragma unroll
+    for (int x = 0; x < 7; x++) {
+        uint32_t v = 0u;
+#pragma unroll
+        for (int y = 0; y < 7; y++) v |= ((win[y] >> x) & 1u) << y;
+        tr[x] = v;
+    }
+    const int k = (dir + 1) & 3;
+    const bool odd = k & 1, flip = (k == 1) || (k == 2), rev = (k >= 2);
+#pragma unroll
+    for (int b = 0; b < 7; b++) {
+        uint32_t t = flip ? (odd ? tr[6 - b] : win[6 - b]) : (odd ? tr[b] : win[b]);
+        V[b] = rev ? bitrev7(t) : t;
+    }
+    // Grid.process_vis(agent_pos=(3,6)) as row bit-ops (walls opaque, goal/empty transparent)
+#pragma unroll
+    for (int j = 0; j < 7; j++) m[j] = 0u;
+    m[6] = 1u << 3;
+#pragma unroll
+    for (int j = 6; j >= 0; j--) {
+        const uint32_t T = ~V[j] & 0x7fu;
+        uint32_t M = m[j];
+#pragma unroll
+        for (int s = 0; s < 6; s++) M |= (M & T & 0x3fu) << 1;  // left-to-right pass
+        const uint32_t e1 = M & T & 0x3fu;
+#pragma unroll
+        for (int s = 0; s < 6; s++) M |= (M & T & 0x7eu) >> 1;  // right-to-left pass
+        const uint32_t e2 = M & T & 0x7eu;
+        m[j] = M;
+        if (j > 0) m[j - 1] |= e1 | (e1 << 1) | e2 | (e2 >> 1);
+    }
+}
+
 struct StepOut {
     const int64_t *actions;
     int64_t action_stride;
@@ -237,6 +308,13 @@ hipError_t launch_env_step(const EnvDev &E, const StepOut &O, bool refill, hipSt
 hipError_t launch_env_full_obs(const EnvDev &E, uint8_t *out, hipStream_t s);
 hipError_t launch_env_refill(const EnvDev &E, bool full, hipStream_t s);
 hipError_t upload_atlas(const uint8_t *atlas_host);
+// full-grid RGB frames (merlin_render.hip); atlas: the device copy of the frame atlas of tile size ts
+hipError_t launch_render_frames(const uint32_t *walls, const int32_t *goal, const int32_t *agent,
+                                const int32_t *map_index, int64_t n_frames, int size, int ts, int highlight,
+                                const uint8_t *atlas, uint8_t *out, uint32_t *err, hipStream_t s);
+hipError_t launch_env_render(const EnvDev &E, const int64_t *index, int64_t n_frames, int ts, int highlight,
+                             const uint8_t *atlas, uint8_t *out, hipStream_t s);
+hipError_t launch_env_snapshot(const EnvDev &E, uint32_t *walls, int32_t *goal, int32_t *agent, hipStream_t s);
 hipError_t launch_obs_expand_f32(const uint32_t *codes, const int64_t *index, int64_t n, float *out,
                                  float scale, int layout, hipStream_t s);
 hipError_t launch_obs_expand_u8(const uint32_t *codes, const int64_t *index, int64_t n, uint8_t *out,

@@ -10,10 +10,11 @@ from .actor_critic import CNNActorCritic, MLPActorCritic
 from .envs import MerlinEnv, MerlinVecEnv
 from .few_shot import FewShotAdapter
 from .ppo import PPO
+from .recording import Recording, record_episodes
 from .rollout_buffer import CodeRolloutBuffer, RolloutBuffer
 from .scenario_creator import ScenarioCreator
 from .utils.utils import get_device, set_seed
 from .utils.utils_rl import compute_gae_standard, layer_init
 
 __all__ = ["CNNActorCritic", "MLPActorCritic", "MerlinEnv", "MerlinVecEnv", "FewShotAdapter", "PPO", "CodeRolloutBuffer",
-           "RolloutBuffer", "ScenarioCreator", "get_device", "set_seed", "compute_gae_standard", "layer_init"]
+           "Recording", "record_episodes", "RolloutBuffer", "ScenarioCreator", "get_device", "set_seed", "compute_gae_standard", "layer_init"]

@@ -26,6 +26,8 @@ DEVERR_BAD_ACTION = 1
 DEVERR_PLACE_OBJ = 2
 DEVERR_BAD_TILE = 4  # merlin_tower_codes_conv3 saw a frame that is no observation (merlin_tower_errors)
 DEVERR_SLOT_EMPTY = 8  # a reset met an empty look-ahead slot with the step fallback off (merlin_env_set_step_fallback)
+DEVERR_BAD_FRAME = 16  # a rendered frame's agent was off the grid / on a wall / dir outside 0..3, or a bad env id
+FRAME_TILES = 22  # MERLIN_FRAME_TILES: tiles of the frame atlas per tile size (include/merlin_hip.h has the order)
 
 DIFFICULTY_IDS = {"easy": 0, "medium": 1, "mediumhard": 2, "hard": 3, "hardest": 4}
 
@@ -184,6 +186,10 @@ def lib():
     L.merlin_group_clip_sgd.argtypes = [i32, vp, vp, vp, i32, C.c_float, C.c_float, vp, vp, vp]
     L.merlin_episode_loss.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp]
     L.merlin_episode_class_stats.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp]
+    L.merlin_frame_atlas.argtypes = [i32, vp]
+    L.merlin_render_frames.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp]
+    L.merlin_env_render.argtypes = [vp, vp, i64, i32, i32, vp, vp]
+    L.merlin_env_snapshot.argtypes = [vp, vp, vp, vp, vp]
     check_env_config_layout(L)
     _lib = L
     return L
@@ -235,6 +241,7 @@ EXPORTED_SYMBOLS = (
     "merlin_window_gemm_fwd",
     "merlin_group_clip_sgd_workspace", "merlin_group_clip_sgd", "merlin_episode_loss",
     "merlin_env_set_difficulties", "merlin_episode_class_stats",
+    "merlin_frame_atlas", "merlin_render_frames", "merlin_env_render", "merlin_env_snapshot",
 )
 
 
@@ -428,6 +435,55 @@ def tile_atlas():
     a = np.zeros((5, 8, 8, 3), dtype=np.uint8)
     check(lib().merlin_tile_atlas(a.ctypes.data_as(C.c_void_p)), "merlin_tile_atlas")
     return a
+
+
+def frame_atlas(tile_size: int):
+    """uint8[22, ts, ts, 3]: the tiles full-grid frames are made of (merlin_frame_atlas; order in
+    include/merlin_hip.h: object + 3 * highlighted, then 6 + ((on_goal * 4 + agent_dir) * 2 + highlighted))."""
+    import numpy as np
+
+    ts = int(tile_size)
+    a = np.zeros((FRAME_TILES, max(ts, 0), max(ts, 0), 3), dtype=np.uint8)
+    if a.size == 0:  # the library refuses the size; give it somewhere to not write
+        a = np.zeros((1,), dtype=np.uint8)
+    check(lib().merlin_frame_atlas(ts, a.ctypes.data_as(C.c_void_p)), "merlin_frame_atlas")
+    return a
+
+
+def frame_tile_index(obj: int, agent_dir: int | None, highlight: bool) -> int:
+    """Atlas index of (object 0 empty / 1 wall / 2 goal, the agent's direction or None, highlighted)."""
+    if agent_dir is None:
+        return int(obj) + 3 * int(bool(highlight))
+    return 6 + (((4 if obj == 2 else 0) + int(agent_dir)) * 2 + int(bool(highlight)))
+
+
+def render_frames(walls: torch.Tensor, goal: torch.Tensor | None, agent: torch.Tensor, size: int,
+                  tile_size: int = 32, highlight: bool = True, map_index: torch.Tensor | None = None,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+    """uint8[F, size*ts, size*ts, 3] full-grid frames of recorded states (merlin_render_frames): walls int32[M, size]
+    bit rows, goal int32[M, 2], agent int32[F, 4] = (x, y, dir, 0); frame f shows map map_index[f] (int32[F]; None: f,
+    then M >= F).  `out`: a contiguous uint8 tensor of that many bytes, any alignment."""
+    S, ts = int(size), int(tile_size)
+    F = int(agent.shape[0])
+    assert agent.dtype == torch.int32 and agent.shape == (F, 4)
+    assert walls.dtype == torch.int32 and walls.dim() == 2 and walls.shape[1] == S
+    M = int(walls.shape[0])
+    assert goal is None or (goal.dtype == torch.int32 and goal.shape == (M, 2))
+    if map_index is None:
+        assert M >= F, "without map_index every frame needs its own map"
+    else:
+        assert map_index.dtype == torch.int32 and map_index.shape == (F,)
+        if F and not (0 <= int(map_index.min()) and int(map_index.max()) < M):
+            raise MerlinNativeError("render_frames: map_index outside [0, M)")
+    side = S * max(ts, 0)
+    if out is None:
+        out = torch.empty((F, side, side, 3), dtype=torch.uint8, device=agent.device)
+    if out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != F * side * side * 3:
+        raise MerlinNativeError(f"render_frames: out must be a contiguous uint8 tensor of {F}x{side}x{side}x3 bytes")
+    with torch.cuda.device(agent.device), KernelTimer.span("k_render_frames", out.numel() + F * (S * 4 + 24)):
+        check(lib().merlin_render_frames(ptr(walls), ptr(goal), ptr(agent), ptr(map_index), F, S, ts,
+                                         int(bool(highlight)), ptr(out), stream_of(agent)), "merlin_render_frames")
+    return out.view(F, side, side, 3)
 
 
 # ---------------------------------------------------------------------------
@@ -829,6 +885,9 @@ def tower_errors(device=None, raise_on_error: bool = True) -> int:
     if raise_on_error and flags.value & DEVERR_BAD_TILE:
         raise MerlinNativeError("merlin_tower_codes_conv3: a frame without the agent tile at view cell (3, 6), or with "
                                 "it elsewhere -- not an observation; its windows were read as other windows")
+    if raise_on_error and flags.value & DEVERR_BAD_FRAME:
+        raise MerlinNativeError("merlin_render_frames: an agent outside the grid, on a wall or with a direction outside "
+                                "0..3; its frame was drawn without the agent")
     return flags.value
 
 def segment_sum(src, plan, out_rows: int, slot=None, sub: int = 1, name: str = "k_seg_sum", out=None,

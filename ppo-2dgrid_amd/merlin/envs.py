@@ -322,6 +322,40 @@ class MerlinVecEnv:
             nat.check(self._lib.merlin_env_full_obs(self._h, nat.ptr(out), self._stream), "merlin_env_full_obs")
         return out
 
+    def render_frames(self, tile_size: int = 32, highlight: bool = True, index: torch.Tensor | None = None,
+                      out: torch.Tensor | None = None) -> torch.Tensor:
+        """uint8[n, size*ts, size*ts, 3] on the device: minigrid's render() in rgb_array mode -- get_frame(highlight,
+        tile_size), the whole grid at ts-pixel tiles, the agent's triangle in its world direction, the cells its view
+        shows brightened -- of every env's current state, or of the envs `index` (int64 env ids) (merlin_env_render).
+        `out`: a contiguous uint8 tensor of exactly that many bytes."""
+        ts = int(tile_size)
+        if index is not None:
+            index = index.to(device=self.device, dtype=torch.int64).contiguous()
+        n = self.num_envs if index is None else int(index.numel())
+        side = self.size * max(ts, 0)
+        if out is None:
+            out = torch.empty((n, side, side, 3), dtype=torch.uint8, device=self.device)
+        if out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != n * side * side * 3:
+            raise nat.MerlinNativeError(f"render_frames: out must be a contiguous uint8 tensor of "
+                                        f"{n}x{side}x{side}x3 bytes")
+        with torch.cuda.device(self.device), nat.KernelTimer.span("k_render_frames", out.numel() + n * 80):
+            nat.check(self._lib.merlin_env_render(self._h, nat.ptr(index), n, ts, int(bool(highlight)), nat.ptr(out),
+                                                  self._stream), "merlin_env_render")
+        return out.view(n, side, side, 3)
+
+    def snapshot(self):
+        """(walls int32[N, size] bit rows, goal int32[N, 2], agent int32[N, 4] = x, y, dir, 0) of the current state
+        as new device tensors, in the layouts merlin._native.render_frames takes (merlin_env_snapshot: one kernel, no
+        host sync)."""
+        n, S = self.num_envs, self.size
+        walls = torch.empty((n, S), dtype=torch.int32, device=self.device)
+        goal = torch.empty((n, 2), dtype=torch.int32, device=self.device)
+        agent = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            nat.check(self._lib.merlin_env_snapshot(self._h, nat.ptr(walls), nat.ptr(goal), nat.ptr(agent),
+                                                    self._stream), "merlin_env_snapshot")
+        return walls, goal, agent
+
     # -- introspection (host syncs; tests / tooling) --------------------------
     def get_state(self) -> dict:
         n, S = self.num_envs, self.size
@@ -354,6 +388,8 @@ class MerlinVecEnv:
             if flags.value & nat.DEVERR_SLOT_EMPTY:
                 what.append("a reset met an empty look-ahead map slot with the step fallback off (refill() was not "
                             "run after every step)")
+            if flags.value & nat.DEVERR_BAD_FRAME:
+                what.append("render_frames was given an env id outside [0, num_envs) or met an agent off the grid")
             raise nat.MerlinNativeError("device env error: " + "; ".join(what))
         return flags.value, fb.value
 
@@ -369,7 +405,13 @@ class MerlinEnv:
     """
 
     def __init__(self, difficulty: str = "mediumhard", size: int = 16, device="cuda", fully_observable: bool = False,
-                 flatten: bool = False, **kw):
+                 flatten: bool = False, render_mode: str | None = None, **kw):
+        if render_mode == "human":
+            raise ValueError("render_mode='human' opens a window, which this library does not; use "
+                             "render_mode='rgb_array' and render(), or ppo_visualization.py, which writes GIFs")
+        if render_mode not in (None, "rgb_array"):
+            raise ValueError(f"Unknown render_mode: {render_mode}")
+        self.render_mode = render_mode
         self.vec = MerlinVecEnv(1, difficulty=difficulty, size=size, device=device, **kw)
         self.action_space = self.vec.action_space
         # the reference's observation options (src/config/scenario.yaml observation.*,
@@ -411,6 +453,14 @@ class MerlinEnv:
             raise IndexError(f"action {action} is not in ThreeActionWrapper's {{0, 1, 2}}")
         r = float(rew[0].item())
         return self._frame(), r, bool(term[0].item()), bool(trunc[0].item()), {}
+
+    def get_frame(self, highlight: bool = True, tile_size: int = 32) -> np.ndarray:
+        """minigrid's get_frame: the uint8[size*ts, size*ts, 3] picture of the whole grid in the current state."""
+        return self.vec.render_frames(tile_size=tile_size, highlight=highlight)[0].cpu().numpy()
+
+    def render(self) -> np.ndarray:
+        """minigrid's render() in rgb_array mode: get_frame(highlight=True, tile_size=32)."""
+        return self.get_frame()
 
     def close(self):
         self.vec.close()

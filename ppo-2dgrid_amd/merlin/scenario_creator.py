@@ -83,7 +83,12 @@ class ScenarioCreator:
         fully_observable: the encoded full grid instead of the RGB partial view; observation.flatten: as a vector)."""
         obs = {"fully_observable": bool(self.obs_cfg.get("fully_observable", False)),
                "flatten": bool(self.obs_cfg.get("flatten", False))}
-        return MerlinEnv(device=device, **self._env_kwargs(difficulty), **obs, **flags)
+        kw = self._env_kwargs(difficulty)
+        # the config's render_mode (rgb_array in every difficulty) reaches the single env, whose render() it names;
+        # the vector env has render_frames() and no mode
+        cfg = self.config["difficulties"][difficulty]
+        flags.setdefault("render_mode", {**self.global_cfg, **cfg.get("params", {})}.get("render_mode"))
+        return MerlinEnv(device=device, **kw, **obs, **flags)
 
     def create_vec_env(self, difficulty, num_envs: int, seed=None, device="cuda", env_offset: int = 0,
                        **flags) -> MerlinVecEnv:
