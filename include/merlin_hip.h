@@ -265,6 +265,27 @@ int merlin_env_render(merlin_env *env, const int64_t *index_dev, int64_t n, int3
  * int32[N][2], agent_dev int32[N][4].  Any pointer may be NULL.  One kernel, no host sync: capturable. */
 int merlin_env_snapshot(merlin_env *env, uint32_t *walls_dev, int32_t *goal_dev, int32_t *agent_dev,
                         void *stream);
+/* Shortest action paths (no reference counterpart).  With the step rule of merlin_env_step -- 0 turn
+ * left, 1 turn right, 2 forward into a non-wall cell, terminating on the forward action whose front cell is the
+ * goal -- dist(x, y, dir) is the least number of actions after which an episode started in that pose terminates, -1
+ * if none does.  The goal cell is an ordinary cell for a pose standing on it (dist 4 or 5 there, never 0).
+ * Stateless, in merlin_render_frames' layouts: query q < n uses map m = map_index_dev[q] (NULL: q) -- walls_dev
+ * uint32[M][size], goal_dev int32[M][2] (a position outside the grid: -1 everywhere) -- and the pose agent_dev[q]
+ * int32[4] = (x, y, dir, 0).  dist_dev int32[n]: dist at the query's pose, -1 as well for a pose outside the grid,
+ * on a wall or with dir outside 0..3.  field_dev (nullable) int16[n][4][size][size], indexed [dir][y][x]: dist of
+ * every pose of the query's map, -1 for walls and unreachable poses; any alignment.  size outside 5..32, negative n
+ * or a null required pointer: MERLIN_E_INVALID; n = 0 is a no-op.  map_index_dev's values are the caller's to keep
+ * inside [0, M).  One kernel, no allocation, no host sync: capturable. */
+int merlin_shortest_paths(const uint32_t *walls_dev, const int32_t *goal_dev, const int32_t *agent_dev,
+                          const int32_t *map_index_dev, int64_t n, int32_t size, int32_t *dist_dev,
+                          int16_t *field_dev, void *stream);
+/* The same kernel on the context's current state: dist_dev int32[N], field_dev (nullable) int16[N][4][size][size].
+ * Reads the maps and poses only: no look-ahead slot, RNG or env state changes. */
+int merlin_env_optimal_steps(merlin_env *env, int32_t *dist_dev, int16_t *field_dev, void *stream);
+/* [host] merlin_shortest_paths on host arrays (query q uses map q), a queue search in plain C++: the library's
+ * CPU-side restatement of the kernel.  field nullable. */
+int merlin_shortest_paths_host(const uint32_t *walls, const int32_t *goal, const int32_t *agent, int64_t n,
+                               int32_t size, int32_t *dist, int16_t *field);
 /* [sync] read-and-clear the device error bits and the fallback-map counter. */
 int merlin_env_errors(merlin_env *env, uint32_t *flags_host, uint32_t *fallbacks_host,
                       void *stream);

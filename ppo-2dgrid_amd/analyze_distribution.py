@@ -9,6 +9,8 @@ mixed-task vector env (merlin.evaluation.evaluate_across_difficulties): zero-sho
 after --adapt_steps clipped SGD(--lr_inner) steps per task on sampled support rollouts of --k_support steps.  Writes
 one JSON file (--out): per difficulty the per-task rewards / steps / losses and their mean and std, and for every
 pair of difficulties the distances of merlin.metrics.task_metrics between their (reward, steps) samples.  No plots.
+--efficiency adds per difficulty an "efficiency" object: the path metrics of merlin.pathing (SPL, success rate, reward
+against the optimum) and each task's shortest path length.
 """
 from __future__ import annotations
 
@@ -43,6 +45,8 @@ def parse_args(argv=None):
     p.add_argument("--lr_inner", type=float, default=0.01)
     p.add_argument("--task_batch", type=int, default=32, help="tasks adapted and scored at once (few-shot)")
     p.add_argument("--out", type=str, default="distribution_analysis.json")
+    p.add_argument("--efficiency", action="store_true",
+                   help="add SPL, success rate and reward ratio against each task's shortest path")
     return p.parse_args(argv)
 
 
@@ -60,6 +64,31 @@ def env_kwargs_of(sc: ScenarioCreator, difficulties):
     if len(set(gens.values())) != len(gens):
         raise ValueError(f"two of {list(gens)} name the same generator")
     return gens, common
+
+
+def add_efficiency(args, gens, env_kwargs, device, per):
+    """per[d]["efficiency"]: path_metrics of d's episodes against the shortest paths of the same seeds (one kernel for
+    all difficulties), and one printed line per difficulty."""
+    from merlin.pathing import optimal_paths, path_metrics
+
+    for flag in ("stuck_penalty", "exploration_bonus"):
+        if env_kwargs.get(flag):
+            raise ValueError(f"--efficiency: {flag} shapes the reward, and success is defined as reward > 0")
+    kw = {k: env_kwargs[k] for k in ("size", "max_steps") if k in env_kwargs}
+    nt = args.num_tasks
+    seeds = [args.base_seed + i for i in range(nt)] * len(args.difficulties)
+    opt, _ = optimal_paths(seeds, difficulty=[gens[d] for d in args.difficulties for _ in range(nt)], device=device,
+                           **kw)
+    size = int(kw.get("size", 16))
+    max_steps = int(kw["max_steps"]) if kw.get("max_steps") else 4 * size * size
+    for j, d in enumerate(args.difficulties):
+        o = opt[j * nt:(j + 1) * nt]
+        m = path_metrics(per[d]["rewards"], per[d]["steps"], o, max_steps)
+        m.pop("per_task")
+        m["opt_steps"] = o
+        per[d]["efficiency"] = m
+        print(f"    {d:<11} spl {m['spl']:.3f} | success {m['success_rate']:.3f} | reward ratio "
+              f"{m['reward_ratio']:.3f} | {m['n_solvable']}/{m['n_tasks']} solvable")
 
 
 def main(argv=None):
@@ -84,6 +113,8 @@ def main(argv=None):
         feats[d] = np.stack([np.asarray(rew, dtype=np.float64), np.asarray(steps, dtype=np.float64)], axis=1)
         print(f"    {d:<11} reward {per[d]['reward_mean']:.3f} +- {per[d]['reward_std']:.3f} | "
               f"steps {per[d]['steps_mean']:.1f} +- {per[d]['steps_std']:.1f}")
+    if args.efficiency:
+        add_efficiency(args, gens, env_kwargs, device, per)
     pairs = {f"{a}|{b}": m for (a, b), m in compare_task_feature_dict(feats).items()}
     out = {"model_path": args.model_path, "difficulties": args.difficulties, "num_tasks": args.num_tasks,
            "base_seed": args.base_seed, "adapt_steps": args.adapt_steps, "lr_inner": args.lr_inner,

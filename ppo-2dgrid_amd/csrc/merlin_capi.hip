@@ -382,6 +382,34 @@ int merlin_env_snapshot(merlin_env *e, uint32_t *walls, int32_t *goal, int32_t *
     return MERLIN_OK;
 }
 
+int merlin_shortest_paths(const uint32_t *walls, const int32_t *goal, const int32_t *agent, const int32_t *map_index,
+                          int64_t n, int32_t size, int32_t *dist, int16_t *field, void *stream) {
+    if (size < 5 || size > 32) return fail(MERLIN_E_INVALID, "grid size must be in [5, 32]");
+    if (n < 0) return fail(MERLIN_E_INVALID, "negative query count");
+    if (n == 0) return MERLIN_OK;
+    if (!walls || !goal || !agent || !dist) return fail(MERLIN_E_INVALID, "null argument");
+    HIP_TRY(merlin::launch_shortest_paths(walls, goal, agent, map_index, n, size, dist, field, (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_env_optimal_steps(merlin_env *e, int32_t *dist, int16_t *field, void *stream) {
+    if (!e) return fail(MERLIN_E_INVALID, "null env");
+    if (!e->has_state) return fail(MERLIN_E_INVALID, "merlin_env_optimal_steps before merlin_env_reset");
+    if (!dist) return fail(MERLIN_E_INVALID, "null output");
+    HIP_TRY(merlin::launch_env_optimal_steps(e->dev, dist, field, (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_shortest_paths_host(const uint32_t *walls, const int32_t *goal, const int32_t *agent, int64_t n,
+                               int32_t size, int32_t *dist, int16_t *field) {
+    if (size < 5 || size > 32) return fail(MERLIN_E_INVALID, "grid size must be in [5, 32]");
+    if (n < 0) return fail(MERLIN_E_INVALID, "negative query count");
+    if (n == 0) return MERLIN_OK;
+    if (!walls || !goal || !agent || !dist) return fail(MERLIN_E_INVALID, "null argument");
+    merlin::shortest_paths_host(walls, goal, agent, n, size, dist, field);
+    return MERLIN_OK;
+}
+
 int64_t merlin_env_config_layout(int64_t *offsets_host, int32_t n_fields) {
     const int64_t off[MERLIN_ENV_CONFIG_FIELDS] = {
         (int64_t)offsetof(merlin_env_config, num_envs),     (int64_t)offsetof(merlin_env_config, size),

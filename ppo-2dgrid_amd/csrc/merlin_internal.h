@@ -315,6 +315,14 @@ hipError_t launch_render_frames(const uint32_t *walls, const int32_t *goal, cons
 hipError_t launch_env_render(const EnvDev &E, const int64_t *index, int64_t n_frames, int ts, int highlight,
                              const uint8_t *atlas, uint8_t *out, hipStream_t s);
 hipError_t launch_env_snapshot(const EnvDev &E, uint32_t *walls, int32_t *goal, int32_t *agent, hipStream_t s);
+// shortest action paths to the goal (merlin_paths.hip): dist int32[n] at each query's pose, field (nullable)
+// int16[n][4][size][size]; one launch, no allocation
+hipError_t launch_shortest_paths(const uint32_t *walls, const int32_t *goal, const int32_t *agent,
+                                 const int32_t *map_index, int64_t n, int size, int32_t *dist, int16_t *field,
+                                 hipStream_t s);
+hipError_t launch_env_optimal_steps(const EnvDev &E, int32_t *dist, int16_t *field, hipStream_t s);
+void shortest_paths_host(const uint32_t *walls, const int32_t *goal, const int32_t *agent, int64_t n, int S,
+                         int32_t *dist, int16_t *field);
 hipError_t launch_obs_expand_f32(const uint32_t *codes, const int64_t *index, int64_t n, float *out,
                                  float scale, int layout, hipStream_t s);
 hipError_t launch_obs_expand_u8(const uint32_t *codes, const int64_t *index, int64_t n, uint8_t *out,

@@ -190,6 +190,9 @@ def lib():
     L.merlin_render_frames.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp]
     L.merlin_env_render.argtypes = [vp, vp, i64, i32, i32, vp, vp]
     L.merlin_env_snapshot.argtypes = [vp, vp, vp, vp, vp]
+    L.merlin_shortest_paths.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp, vp]
+    L.merlin_env_optimal_steps.argtypes = [vp, vp, vp, vp]
+    L.merlin_shortest_paths_host.argtypes = [vp, vp, vp, i64, i32, vp, vp]
     check_env_config_layout(L)
     _lib = L
     return L
@@ -242,6 +245,7 @@ EXPORTED_SYMBOLS = (
     "merlin_group_clip_sgd_workspace", "merlin_group_clip_sgd", "merlin_episode_loss",
     "merlin_env_set_difficulties", "merlin_episode_class_stats",
     "merlin_frame_atlas", "merlin_render_frames", "merlin_env_render", "merlin_env_snapshot",
+    "merlin_shortest_paths", "merlin_env_optimal_steps", "merlin_shortest_paths_host",
 )
 
 
@@ -484,6 +488,64 @@ def render_frames(walls: torch.Tensor, goal: torch.Tensor | None, agent: torch.T
         check(lib().merlin_render_frames(ptr(walls), ptr(goal), ptr(agent), ptr(map_index), F, S, ts,
                                          int(bool(highlight)), ptr(out), stream_of(agent)), "merlin_render_frames")
     return out.view(F, side, side, 3)
+
+
+def shortest_paths_bytes(n: int, size: int, field: bool) -> int:
+    """Algorithmic bytes of k_shortest_paths: the rows, pose and goal read, dist and (twice: the -1 fill and the
+    values) the field written."""
+    return n * (size * 4 + 32 + (2 * 8 * size * size if field else 0))
+
+
+def shortest_paths(walls: torch.Tensor, goal: torch.Tensor, agent: torch.Tensor, size: int,
+                   map_index: torch.Tensor | None = None, field: bool = False):
+    """int32[n]: the least number of actions after which an episode started in pose agent[q] = (x, y, dir, 0) on map
+    map_index[q] (int32[n]; None: q, then M >= n) reaches the goal, -1 if none does or the pose is no free cell of the
+    grid (merlin_shortest_paths; include/merlin_hip.h has the definition).  walls int32[M, size] bit rows, goal
+    int32[M, 2], as MerlinVecEnv.snapshot() gives them.  field=True: (dist, int16[n, 4, size, size]), the distance of
+    every pose of each query's map indexed [dir][y][x]."""
+    S = int(size)
+    n = int(agent.shape[0])
+    assert agent.dtype == torch.int32 and agent.shape == (n, 4)
+    assert walls.dtype == torch.int32 and walls.dim() == 2 and walls.shape[1] == S
+    M = int(walls.shape[0])
+    assert goal.dtype == torch.int32 and goal.shape == (M, 2)
+    if map_index is None:
+        assert M >= n, "without map_index every query needs its own map"
+    else:
+        assert map_index.dtype == torch.int32 and map_index.shape == (n,)
+        if n and not (0 <= int(map_index.min()) and int(map_index.max()) < M):
+            raise MerlinNativeError("shortest_paths: map_index outside [0, M)")
+    dist = torch.empty((n,), dtype=torch.int32, device=agent.device)
+    fld = torch.empty((n, 4, max(S, 0), max(S, 0)), dtype=torch.int16, device=agent.device) if field else None
+    with torch.cuda.device(agent.device), KernelTimer.span("k_shortest_paths", shortest_paths_bytes(n, S, field)):
+        check(lib().merlin_shortest_paths(ptr(walls), ptr(goal), ptr(agent), ptr(map_index), n, S, ptr(dist),
+                                          ptr(fld), stream_of(agent)), "merlin_shortest_paths")
+    return (dist, fld) if field else dist
+
+
+def shortest_paths_host(walls, goal, agent, size: int, field: bool = False):
+    """shortest_paths on numpy arrays, solved on the CPU by the library's queue search (merlin_shortest_paths_host):
+    walls uint32 / int32 [n, size], goal int32[n, 2], agent int32[n, 4]; query q uses map q."""
+    import numpy as np
+
+    S = int(size)
+    agent = np.ascontiguousarray(agent, dtype=np.int32)
+    n = int(agent.shape[0])
+    assert agent.shape == (n, 4)
+    walls = np.ascontiguousarray(np.asarray(walls).astype(np.uint32, copy=False))
+    goal = np.ascontiguousarray(goal, dtype=np.int32)
+    assert walls.shape == (n, S) and goal.shape == (n, 2)
+    dist = np.empty((n,), dtype=np.int32)
+    fld = np.empty((n, 4, max(S, 0), max(S, 0)), dtype=np.int16) if field else None
+    vp = C.c_void_p
+    # a span of its own name: on an idle stream the event pair brackets the host call, and the kernel's statistics
+    # stay the kernel's
+    with KernelTimer.span("shortest_paths_host", shortest_paths_bytes(n, S, field)):
+        check(lib().merlin_shortest_paths_host(walls.ctypes.data_as(vp), goal.ctypes.data_as(vp),
+                                               agent.ctypes.data_as(vp), n, S, dist.ctypes.data_as(vp),
+                                               fld.ctypes.data_as(vp) if field else None),
+              "merlin_shortest_paths_host")
+    return (dist, fld) if field else dist
 
 
 # ---------------------------------------------------------------------------

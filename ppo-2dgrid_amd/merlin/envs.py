@@ -356,6 +356,37 @@ class MerlinVecEnv:
                                                     self._stream), "merlin_env_snapshot")
         return walls, goal, agent
 
+    # -- shortest action paths (merlin/pathing.py) -----------------------------
+    def optimal_steps(self, out: torch.Tensor | None = None) -> torch.Tensor:
+        """int32[N]: the least number of actions after which each env, from its current pose, can terminate at its
+        goal; -1 if none does (merlin_env_optimal_steps: one kernel, no allocation beyond `out`, no host sync; reads
+        the maps and poses only)."""
+        return self._optimal(out, None)
+
+    def distance_field(self, out: torch.Tensor | None = None):
+        """(dist int32[N], field int16[N, 4, size, size]): optimal_steps() and the same distance for every pose of
+        each env's map, indexed [dir][y][x]; -1 for walls and poses the goal cannot be reached from.  `out`: the
+        field's buffer, a contiguous int16 tensor of that many elements at any alignment."""
+        S = self.size
+        if out is None:
+            out = torch.empty((self.num_envs, 4, S, S), dtype=torch.int16, device=self.device)
+        if out.dtype != torch.int16 or not out.is_contiguous() or out.numel() != self.num_envs * 4 * S * S:
+            raise nat.MerlinNativeError(f"distance_field: out must be a contiguous int16 tensor of "
+                                        f"{self.num_envs}x4x{S}x{S} elements")
+        return self._optimal(None, out), out
+
+    def _optimal(self, out, field):
+        n = self.num_envs
+        if out is None:
+            out = torch.empty((n,), dtype=torch.int32, device=self.device)
+        if out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != n:
+            raise nat.MerlinNativeError(f"optimal_steps: out must be a contiguous int32 tensor of {n} elements")
+        with torch.cuda.device(self.device), nat.KernelTimer.span(
+                "k_shortest_paths", nat.shortest_paths_bytes(n, self.size, field is not None)):
+            nat.check(self._lib.merlin_env_optimal_steps(self._h, nat.ptr(out), nat.ptr(field), self._stream),
+                      "merlin_env_optimal_steps")
+        return out
+
     # -- introspection (host syncs; tests / tooling) --------------------------
     def get_state(self) -> dict:
         n, S = self.num_envs, self.size
@@ -453,6 +484,11 @@ class MerlinEnv:
             raise IndexError(f"action {action} is not in ThreeActionWrapper's {{0, 1, 2}}")
         r = float(rew[0].item())
         return self._frame(), r, bool(term[0].item()), bool(trunc[0].item()), {}
+
+    def optimal_steps(self) -> int:
+        """The least number of actions after which the env, from its current pose, can terminate at the goal; -1 if
+        it cannot (MerlinVecEnv.optimal_steps)."""
+        return int(self.vec.optimal_steps()[0].item())
 
     def get_frame(self, highlight: bool = True, tile_size: int = 32) -> np.ndarray:
         """minigrid's get_frame: the uint8[size*ts, size*ts, 3] picture of the whole grid in the current state."""

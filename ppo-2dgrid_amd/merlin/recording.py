@@ -89,6 +89,17 @@ class Recording:
         finally:
             env.close()
 
+    # -- shortest paths ---------------------------------------------------------------------------------------------
+    def optimal_steps(self) -> torch.Tensor:
+        """int64[n] on the host: the least number of actions after which each recorded episode could have terminated
+        at its goal from its start pose, -1 where none does (merlin._native.shortest_paths on the recording's own maps;
+        merlin/pathing.py has the metrics built on it)."""
+        if not self.num_envs:
+            return torch.zeros(0, dtype=torch.int64)
+        dist = nat.shortest_paths(self.walls.to(self.device), self.goal.to(self.device),
+                                  self.agent[0].contiguous().to(self.device), self.size)
+        return dist.cpu().long()
+
     # -- pixels -----------------------------------------------------------------------------------------------------
     def _range(self, i: int, start: int, stop):
         last = int(self.lengths[i]) + 1  # step 0 is the reset state
