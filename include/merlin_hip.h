@@ -67,8 +67,7 @@
  * evaluation (merlin_group_clip_sgd, merlin_episode_loss: src/distribution_over_tasks.py:97-128, :200-203) -- or
  * are ALTERNATE forms kept selectable for A/B and float64 precision tests: merlin_x6_* (fc1 in six bf16
  * products, rounds 2-3), merlin_h3_gemm_nt / _tn / _tn_planes / _nt_gather with the register-staged
- * configurations (round 4).  Probe-only configurations (kernel ablations that compute wrong results on purpose)
- * exist only in a -DMERLIN_PROBES build.
+ * configurations (round 4).
  */
 #ifndef MERLIN_HIP_H
 #define MERLIN_HIP_H
@@ -630,9 +629,12 @@ int merlin_tower_heads_fwd(const float *h_dev, int64_t n, int32_t hidden, const 
  * split / join: n fp32 values (n % 8 == 0) <-> their planes (6 bytes per value).
  * gemm_nt:  C[t][m][n] = sum_k A[t][m][k] B[t][n][k], A fp32 [M][K], B planes [N][K] (K % 32 == 0;
  *           tower strides in values), + bias[t][n] and ReLU when bias != NULL; cfg selects the tile
- *           (0: 256x128, 1: 128x192, 2: 128x128, 3: 256x64; N a multiple of the tile width).
+ *           (0: 256x128, 1: 128x192, 2: 128x128, 3: 256x64; N a multiple of the tile width; 20..28 the
+ *           32x32x16 MFMA kernels of csrc/merlin_gemm2.hip: 20 / 21 / 24 / 26 256x128, 22 / 23 / 27 128x192,
+ *           25 / 28 128x128).  Any other cfg: MERLIN_E_UNSUPPORTED.
  * gemm_tn:  out[t][m][n] = sum_k A[t][k][m] B[t][k][n], A fp32 [Kd][M], B fp32 [Kd][N] (M, N multiples
- *           of the tile: cfg 0 / 2: 128x192, 1: 128x64), the k range cut into <= splits slabs
+ *           of the tile: cfg 0 / 2: 128x192, 1: 128x64; 20 / 21: 128x192 and 24 / 25: 256x192 on the
+ *           32x32x16 MFMA), the k range cut into <= splits slabs
  *           (slab float[merlin_x6_tn_slab_floats(...)]) summed in slab order. */
 int merlin_x6_split(const float *x_dev, int64_t n, void *planes_dev, void *stream);
 int merlin_x6_join(const void *planes_dev, int64_t n, float *x_dev, void *stream);
@@ -656,11 +658,13 @@ int merlin_x6_gemm_tn(const float *A_dev, const float *B_dev, int64_t Kd, int32_
  *        exponent of amax_dev[t]; 4 bytes per value.
  * gemm_nt: C[t][m][n] = sum_k A[t][m][k] B[t][n][k], A fp32 [M][K] with its amax, B planes [N][K] (K % 32 == 0;
  *          tower strides in values), + bias[t][n] and ReLU when bias != NULL; cfg: 0 256x128, 1 128x192,
- *          2 128x128, 3 128x256 (N a multiple of the tile width), 10..13 the same tiles with the split interleaved
- *          into the MFMAs (K >= 64).  a_planes_dev (nullable): receives A's planes as the kernel makes them
+ *          2 128x128, 3 128x256, 5 128x64 (N a multiple of the tile width), 10..13 the same tiles as 0..3 with the
+ *          split interleaved into the MFMAs (K >= 64), 14 the same at 64x128; 20 / 21 (256x128 / 128x192) both
+ *          operands staged into LDS by DMA, 30 / 31 the same with the fragment reads under the MFMAs.  Any other cfg:
+ *          MERLIN_E_UNSUPPORTED.  a_planes_dev (nullable; cfg < 20): receives A's planes as the kernel makes them
  *          ([t][M][K/8][2][8] f16, A's byte layout and tower stride) for a later gemm_tn_planes.
  * gemm_tn: out[t][m][n] = sum_k A[t][k][m] B[t][k][n], both fp32 with their amax (cfg 0 / 1: 128x192 tiles, M % 128,
- *          N % 192), the k range cut into <= splits slabs (slab float[merlin_x6_tn_slab_floats(...)]) summed in slab
+ *          N % 192; 2: 64x192; 10 / 11: 0 / 1 with the split interleaved into the MFMAs), the k range cut into <= splits slabs (slab float[merlin_x6_tn_slab_floats(...)]) summed in slab
  *          order.
  * gemm_tn_planes: the same product over operands already in plane form (the a_planes output of gemm_nt for the same
  *          tensor and amax), strides in values.

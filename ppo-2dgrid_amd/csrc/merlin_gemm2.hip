@@ -52,10 +52,9 @@ __device__ __forceinline__ void split8(const float4 a, const float4 b, u32x4 &p0
     p2 = u32x4{x[2].x, x[2].y, y[2].x, y[2].y};
 }
 
-// C[t][m][n] = epi(sum_k A[t][m][k] B[t][n][k]); A fp32 [M][K] (APL 0, split while staged) or x6
-// planes [M][K/8][3][8] (APL 1, staged as copies like B), B x6 planes [N][K/8][3][8] (K % 32 == 0,
-// N % BN == 0); EPI 1: relu(. + bias[t][n]).  grid (tiles_m * tiles_n, T).
-template <int BM, int BN, int WGM, int WGN, int EPI, int ACC, int APL = 0>
+// C[t][m][n] = epi(sum_k A[t][m][k] B[t][n][k]); A fp32 [M][K] (split while staged), B x6 planes
+// [N][K/8][3][8] (K % 32 == 0, N % BN == 0); EPI 1: relu(. + bias[t][n]).  grid (tiles_m * tiles_n, T).
+template <int BM, int BN, int WGM, int WGN, int EPI, int ACC>
 __global__ __launch_bounds__(64 * WGM * WGN) void k_x6_nt32(const void *__restrict__ Av, const u32x4 *__restrict__ B,
                                                             int64_t M, int N, int K, int64_t sA, int64_t sB,
                                                             const float *__restrict__ bias, float *__restrict__ C,
@@ -63,10 +62,10 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_x6_nt32(const void *__restri
     constexpr int NT = 64 * WGM * WGN;
     constexpr int WTM = BM / WGM, WTN = BN / WGN;
     constexpr int TM = WTM / 32, TN = WTN / 32;
-    constexpr int UA = APL ? (BM * CPR + NT - 1) / NT : (BM * 4 + NT - 1) / NT;  // A chunks / fp32 units
+    constexpr int UA = (BM * 4 + NT - 1) / NT;  // A fp32 units
     constexpr int CB = (BN * CPR + NT - 1) / NT;
     static_assert(WTM % 32 == 0 && WTN % 32 == 0, "wave tile of 32 x 32 MFMA tiles");
-    constexpr int PSA = BM * 4 + (APL ? 12 : 0), PSB = BN * 4 + 12;
+    constexpr int PSA = BM * 4, PSB = BN * 4 + 12;
     constexpr int STAGE = 3 * (PSA + PSB);
     __shared__ u32x4 lds[2 * STAGE];
 
@@ -75,28 +74,20 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_x6_nt32(const void *__restri
     const int tm = L / tiles_n, tn = L - tm * tiles_n;
     const int64_t m0 = (int64_t)tm * BM;
     const int n0 = tn * BN;
-    const int64_t rowA = APL ? (int64_t)(K / 8) * 3 : K / 4;  // A row in chunks (planes) / float4s
+    const int64_t rowA = K / 4;  // A row in float4s
     const int64_t rowB = (int64_t)(K / 8) * 3;
     B += t * sB;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int wm = w / WGN, wn = w - (w / WGN) * WGN;
 
-    const float4 *ga[APL ? 1 : UA];
-    const u32x4 *Ap = static_cast<const u32x4 *>(Av) + t * sA;
-    int gp[APL ? UA : 1];  // planes: chunk offsets from Ap (32-bit: fewer address registers)
+    const float4 *ga[UA];
     int la[UA];
 #pragma unroll
     for (int i = 0; i < UA; i++) {
         const int q = tid + i * NT;
-        if constexpr (APL) {
-            const int row = std::min(q / CPR, BM - 1), rem = q - (q / CPR) * CPR, p = rem >> 2, g = rem & 3;
-            gp[i] = (int)(std::min<int64_t>(m0 + row, M - 1) * rowA + g * 3 + p);
-            la[i] = p * PSA + row * 4 + (g ^ ((row >> 2) & 3));
-        } else {
-            const int row = std::min(q >> 2, BM - 1), g = q & 3;
-            ga[i] = static_cast<const float4 *>(Av) + t * sA + std::min<int64_t>(m0 + row, M - 1) * rowA + g * 2;
-            la[i] = row * 4 + (g ^ ((row >> 2) & 3));
-        }
+        const int row = std::min(q >> 2, BM - 1), g = q & 3;
+        ga[i] = static_cast<const float4 *>(Av) + t * sA + std::min<int64_t>(m0 + row, M - 1) * rowA + g * 2;
+        la[i] = row * 4 + (g ^ ((row >> 2) & 3));
     }
     int gb[CB];  // chunk offsets from B (the weights: N * K * 3 / 8 chunks, well inside 32 bits)
     int lb[CB];
@@ -107,18 +98,13 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_x6_nt32(const void *__restri
         gb[i] = (int)((int64_t)(n0 + std::min(row, BN - 1)) * rowB + g * 3 + p);
         lb[i] = 3 * PSA + p * PSB + row * 4 + (g ^ ((row >> 2) & 3));
     }
-    float4 ra[APL ? 1 : UA][2];
-    u32x4 rp[APL ? UA : 1];
+    float4 ra[UA][2];
     u32x4 rb[CB];
     auto load = [&](int kt) {
 #pragma unroll
         for (int i = 0; i < UA; i++) {
-            if constexpr (APL) {
-                rp[i] = Ap[gp[i] + kt * CPR];
-            } else {
-                ra[i][0] = ga[i][(int64_t)kt * 8];
-                ra[i][1] = ga[i][(int64_t)kt * 8 + 1];
-            }
+            ra[i][0] = ga[i][(int64_t)kt * 8];
+            ra[i][1] = ga[i][(int64_t)kt * 8 + 1];
         }
 #pragma unroll
         for (int i = 0; i < CB; i++) rb[i] = B[gb[i] + kt * CPR];
@@ -126,17 +112,14 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_x6_nt32(const void *__restri
     auto store = [&](int buf) {
         u32x4 *st = lds + buf * STAGE;
 #pragma unroll
-        for (int i = 0; i < UA; i++) {
-            if constexpr (APL) {
-                if ((BM * CPR) % NT == 0 || i + 1 < UA || tid + i * NT < BM * CPR) st[la[i]] = rp[i];
-            } else if ((BM * 4) % NT == 0 || i + 1 < UA || tid + i * NT < BM * 4) {
+        for (int i = 0; i < UA; i++)
+            if ((BM * 4) % NT == 0 || i + 1 < UA || tid + i * NT < BM * 4) {
                 u32x4 p0, p1, p2;
                 split8(ra[i][0], ra[i][1], p0, p1, p2);
                 st[la[i]] = p0;
                 st[PSA + la[i]] = p1;
                 st[2 * PSA + la[i]] = p2;
             }
-        }
 #pragma unroll
         for (int i = 0; i < CB; i++)
             if ((BN * CPR) % NT == 0 || i + 1 < CB || tid + i * NT < BN * CPR) st[lb[i]] = rb[i];
@@ -264,9 +247,7 @@ __device__ __forceinline__ u32x4 tr32_frag(const u32x4 *img, int col0, int kh, i
     return __builtin_bit_cast(u32x4, bf16x8{v[0][0], v[0][1], v[0][2], v[0][3], v[1][0], v[1][1], v[1][2], v[1][3]});
 }
 
-// PL 1: both operands already in x6 planes ([Kd][M/8][3][8], [Kd][N/8][3][8]), staged as 16-B chunk
-// copies (no split work in the loop).
-template <int BM, int BN, int WGM, int WGN, int PL = 0>
+template <int BM, int BN, int WGM, int WGN>
 __global__ __launch_bounds__(64 * WGM * WGN) void k_x6_tn32(const void *__restrict__ Av, const void *__restrict__ Bv,
                                                             int64_t Kd, int M, int N, int64_t sA, int64_t sB,
                                                             int64_t kc, int tiles_n, int tiles, int S,
@@ -275,7 +256,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_x6_tn32(const void *__restri
     constexpr int WTM = BM / WGM, WTN = BN / WGN;
     constexpr int TM = WTM / 32, TN = WTN / 32;
     constexpr int RCA = BM / 8, RCB = BN / 8;
-    constexpr int QA = BK * RCA * (PL ? 3 : 1), QB = BK * RCB * (PL ? 3 : 1);  // units (chunks) per k step
+    constexpr int QA = BK * RCA, QB = BK * RCB;  // units per k step
     constexpr int UA = (QA + NT - 1) / NT, UB = (QB + NT - 1) / NT;
     static_assert(WTM % 32 == 0 && WTN % 32 == 0, "wave tile of 32 x 32 MFMA tiles");
     constexpr int PSA = BK * RCA, PSB = BK * RCB;
@@ -289,10 +270,10 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_x6_tn32(const void *__restri
     const int tm = L / tiles_n, tn = L - tm * tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
     const int64_t k0 = (int64_t)s * kc, k1 = std::min<int64_t>(Kd, k0 + kc);
-    // rows in float4s (fp32) or 16-B chunks (planes); the tile's first column in the same unit
-    const int64_t rowA = PL ? M / 8 * 3 : M / 4, rowB = PL ? N / 8 * 3 : N / 4;
-    const float4 *A = static_cast<const float4 *>(Av) + t * sA + (PL ? m0 / 8 * 3 : m0 / 4);
-    const float4 *B = static_cast<const float4 *>(Bv) + t * sB + (PL ? n0 / 8 * 3 : n0 / 4);
+    // rows in float4s; the tile's first column in the same unit
+    const int64_t rowA = M / 4, rowB = N / 4;
+    const float4 *A = static_cast<const float4 *>(Av) + t * sA + m0 / 4;
+    const float4 *B = static_cast<const float4 *>(Bv) + t * sB + n0 / 4;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int wm = w / WGN, wn = w - (w / WGN) * WGN;
 
@@ -300,36 +281,22 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_x6_tn32(const void *__restri
 #pragma unroll
     for (int i = 0; i < UA; i++) {
         const int q = std::min(tid + i * NT, QA - 1);
-        if constexpr (PL) {  // chunk (k, g, p): memory order within a k row is [g][p]
-            const int k = q / (RCA * 3), rem = q - k * (RCA * 3), g = rem / 3, p = rem - g * 3;
-            ka[i] = k;
-            oa[i] = rem;
-            la[i] = p * PSA + k * RCA + (g ^ tr32_swz<RCA>(k));
-        } else {
-            const int k = q / RCA, g = q - (q / RCA) * RCA;
-            ka[i] = k;
-            oa[i] = g * 2;
-            la[i] = k * RCA + (g ^ tr32_swz<RCA>(k));
-        }
+        const int k = q / RCA, g = q - (q / RCA) * RCA;
+        ka[i] = k;
+        oa[i] = g * 2;
+        la[i] = k * RCA + (g ^ tr32_swz<RCA>(k));
     }
     int kb[UB], ob[UB], lb[UB];
 #pragma unroll
     for (int i = 0; i < UB; i++) {
         const int q = std::min(tid + i * NT, QB - 1);
-        if constexpr (PL) {
-            const int k = q / (RCB * 3), rem = q - k * (RCB * 3), g = rem / 3, p = rem - g * 3;
-            kb[i] = k;
-            ob[i] = rem;
-            lb[i] = 3 * PSA + p * PSB + k * RCB + (g ^ tr32_swz<RCB>(k));
-        } else {
-            const int k = q / RCB, g = q - (q / RCB) * RCB;
-            kb[i] = k;
-            ob[i] = g * 2;
-            lb[i] = 3 * PSA + k * RCB + (g ^ tr32_swz<RCB>(k));
-        }
+        const int k = q / RCB, g = q - (q / RCB) * RCB;
+        kb[i] = k;
+        ob[i] = g * 2;
+        lb[i] = 3 * PSA + k * RCB + (g ^ tr32_swz<RCB>(k));
     }
     const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    constexpr int W = PL ? 1 : 2;  // float4s per unit
+    constexpr int W = 2;  // float4s per unit
     float4 ra[UA][W], rb[UB][W];
     // full steps (every one but a split's last) read row pointers + a wave-uniform offset (no per-lane clamp)
     const float4 *pa[UA], *pb[UB];
@@ -371,29 +338,21 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_x6_tn32(const void *__restri
         for (int i = 0; i < UA; i++)
             if (QA % NT == 0 || i + 1 < UA || tid + i * NT < QA) {
                 const bool in = kk + ka[i] < k1;
-                if constexpr (PL) {
-                    st[la[i]] = __builtin_bit_cast(u32x4, in ? ra[i][0] : zero);
-                } else {
-                    u32x4 p0, p1, p2;
-                    split8(in ? ra[i][0] : zero, in ? ra[i][W - 1] : zero, p0, p1, p2);
-                    st[la[i]] = p0;
-                    st[PSA + la[i]] = p1;
-                    st[2 * PSA + la[i]] = p2;
-                }
+                u32x4 p0, p1, p2;
+                split8(in ? ra[i][0] : zero, in ? ra[i][W - 1] : zero, p0, p1, p2);
+                st[la[i]] = p0;
+                st[PSA + la[i]] = p1;
+                st[2 * PSA + la[i]] = p2;
             }
 #pragma unroll
         for (int i = 0; i < UB; i++)
             if (QB % NT == 0 || i + 1 < UB || tid + i * NT < QB) {
                 const bool in = kk + kb[i] < k1;
-                if constexpr (PL) {
-                    st[lb[i]] = __builtin_bit_cast(u32x4, in ? rb[i][0] : zero);
-                } else {
-                    u32x4 p0, p1, p2;
-                    split8(in ? rb[i][0] : zero, in ? rb[i][W - 1] : zero, p0, p1, p2);
-                    st[lb[i]] = p0;
-                    st[PSB + lb[i]] = p1;
-                    st[2 * PSB + lb[i]] = p2;
-                }
+                u32x4 p0, p1, p2;
+                split8(in ? rb[i][0] : zero, in ? rb[i][W - 1] : zero, p0, p1, p2);
+                st[lb[i]] = p0;
+                st[PSB + lb[i]] = p1;
+                st[2 * PSB + lb[i]] = p2;
             }
     };
 
@@ -809,27 +768,26 @@ hipError_t nt32b_launch(const float *A, const u32x4 *B, int64_t M, int N, int K,
     return hipGetLastError();
 }
 
-template <int BM, int BN, int WGM, int WGN, int ACC, int APL = 0>
+template <int BM, int BN, int WGM, int WGN, int ACC>
 hipError_t nt32_launch(const void *A, const u32x4 *B, int64_t M, int N, int K, int T, int64_t sA, int64_t sB,
                        const float *bias, float *C, int64_t sC, hipStream_t s) {
     if (N % BN) return hipErrorInvalidValue;
-    // planes-A form: the kernel keeps A chunk offsets (and B's, N * K * 3 / 8) in 32 bits
-    if (APL && (M + BM) * ((int64_t)(K / 8) * 3) > INT32_MAX) return hipErrorInvalidValue;
+    // the kernel keeps B's chunk offsets (N * K * 3 / 8) in 32 bits
     if ((int64_t)N * (K / 8) * 3 > INT32_MAX) return hipErrorInvalidValue;
     const int64_t tiles_m = (M + BM - 1) / BM;
     const int tiles_n = N / BN;
     if (tiles_m * tiles_n > INT32_MAX) return hipErrorInvalidValue;
     const dim3 grid((unsigned)(tiles_m * tiles_n), T);
     if (bias)
-        hipLaunchKernelGGL((k_x6_nt32<BM, BN, WGM, WGN, 1, ACC, APL>), grid, dim3(64 * WGM * WGN), 0, s, A, B, M, N, K,
+        hipLaunchKernelGGL((k_x6_nt32<BM, BN, WGM, WGN, 1, ACC>), grid, dim3(64 * WGM * WGN), 0, s, A, B, M, N, K,
                            sA, sB, bias, C, sC, tiles_n);
     else
-        hipLaunchKernelGGL((k_x6_nt32<BM, BN, WGM, WGN, 0, ACC, APL>), grid, dim3(64 * WGM * WGN), 0, s, A, B, M, N, K,
+        hipLaunchKernelGGL((k_x6_nt32<BM, BN, WGM, WGN, 0, ACC>), grid, dim3(64 * WGM * WGN), 0, s, A, B, M, N, K,
                            sA, sB, nullptr, C, sC, tiles_n);
     return hipGetLastError();
 }
 
-template <int BM, int BN, int WGM, int WGN, int PL = 0>
+template <int BM, int BN, int WGM, int WGN>
 hipError_t tn32_launch(const void *A, const void *B, int64_t Kd, int M, int N, int T, int64_t sA, int64_t sB,
                        int splits, float *slab, hipStream_t s, int *S_out) {
     if (M % BM || N % BN) return hipErrorInvalidValue;
@@ -839,7 +797,7 @@ hipError_t tn32_launch(const void *A, const void *B, int64_t Kd, int M, int N, i
     kc = (kc + BK - 1) / BK * BK;
     S = (int)std::max<int64_t>(1, (Kd + kc - 1) / kc);
     *S_out = S;
-    hipLaunchKernelGGL((k_x6_tn32<BM, BN, WGM, WGN, PL>), dim3(tiles * S * T), dim3(64 * WGM * WGN), 0, s, A, B, Kd, M, N,
+    hipLaunchKernelGGL((k_x6_tn32<BM, BN, WGM, WGN>), dim3(tiles * S * T), dim3(64 * WGM * WGN), 0, s, A, B, Kd, M, N,
                        sA, sB, kc, tiles_n, tiles, S, slab);
     return hipGetLastError();
 }
@@ -850,13 +808,6 @@ hipError_t tn32_launch(const void *A, const void *B, int64_t Kd, int M, int N, i
 // actually used comes back in *S_out for the fold
 hipError_t launch_x6_gemm_tn32(const float *A, const float *B, int64_t Kd, int M, int N, int T, int64_t a_stride,
                                int64_t b_stride, int splits, float *slab, int cfg, hipStream_t s, int *S_out) {
-    if (cfg >= 30) {  // both operands as x6 planes (strides in values: 3 chunks per 8)
-        const int64_t sA = a_stride / 8 * 3, sB = b_stride / 8 * 3;
-        switch (cfg) {
-            case 30: return tn32_launch<128, 192, 4, 2, 1>(A, B, Kd, M, N, T, sA, sB, splits, slab, s, S_out);
-            default: return hipErrorInvalidValue;
-        }
-    }
     const int64_t sA = a_stride / 4, sB = b_stride / 4;
     const float *a = A, *b = B;
     switch (cfg) {
@@ -876,14 +827,6 @@ hipError_t launch_x6_gemm_nt32(const float *A, const void *B, int64_t M, int N, 
                                hipStream_t s) {
     const u32x4 *b = static_cast<const u32x4 *>(B);
     const int64_t sB = b_stride / 8 * 3;
-    if (cfg >= 30) {  // A as x6 planes too (a_stride in values: 3 chunks per 8)
-        const int64_t sA = a_stride / 8 * 3;
-        switch (cfg) {
-            case 30: return nt32_launch<256, 128, 4, 2, 1, 1>(A, b, M, N, K, T, sA, sB, bias, C, c_stride, s);
-            case 32: return nt32_launch<128, 192, 4, 2, 1, 1>(A, b, M, N, K, T, sA, sB, bias, C, c_stride, s);
-            default: return hipErrorInvalidValue;
-        }
-    }
     const float *a = A;
     const int64_t sA = a_stride / 4;
     switch (cfg) {
@@ -891,8 +834,6 @@ hipError_t launch_x6_gemm_nt32(const float *A, const void *B, int64_t M, int N, 
         case 26: return nt32b_launch<256, 128, 2, 2>(a, b, M, N, K, T, sA, sB, bias, C, c_stride, s);
         case 27: return nt32b_launch<128, 192, 2, 2>(a, b, M, N, K, T, sA, sB, bias, C, c_stride, s);
         case 28: return nt32b_launch<128, 128, 2, 2>(a, b, M, N, K, T, sA, sB, bias, C, c_stride, s);
-        // small row counts (the rollout's fc1: 4,096 rows): 64 x 128 tiles, twice the blocks
-        case 29: return nt32b_launch<64, 128, 2, 2>(a, b, M, N, K, T, sA, sB, bias, C, c_stride, s);
         // forward shape (N = 512): 256 x 128 blocks, 8 waves of 64 x 64
         case 20: return nt32_launch<256, 128, 4, 2, 1>(a, b, M, N, K, T, sA, sB, bias, C, c_stride, s);
         case 21: return nt32_launch<256, 128, 4, 2, 0>(a, b, M, N, K, T, sA, sB, bias, C, c_stride, s);

@@ -575,16 +575,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_ntpg(const float *__restr
 // counted vmcnt: the DMA of step kt + 2 stays in flight across the barrier that publishes step kt + 1.
 __device__ __forceinline__ int g_swz(int r) { return (r >> 1) & 7; }
 
-// AP: A arrives as plane images too ([M][K/8][2][8] f16, h3_split's layout: 4 B per value like fp32, so the DMA
-// addressing is the same) -- no split at all, A's fragments read like B's.
-// ABL (probe ablations, round 5): 1 = no DMA in the main loop (compute on whatever the stages hold), 2 = no MFMAs
-// (fragment reads kept live), 3 = neither fragment reads nor MFMAs (the DMA stream alone)
-// ORD (round 5): in the first half step the MFMAs are issued before the reads of the second half -- with the reads
-// first, hipcc waits lgkmcnt(0) for them before the first MFMA (the MFMAs' operands come from the reads issued after
-// the previous barrier, and it does not count the newer ones out), so every other half step's MFMAs waited for a
-// full LDS read round trip (the .s of cfg 42)
-template <int BM, int BN, int WGM, int WGN, int EPI, bool KP, bool AP = false, bool PR = false, int ABL = 0,
-          bool ORD = false>
+template <int BM, int BN, int WGM, int WGN, int EPI, bool KP>
 __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_ntg(const float *__restrict__ A, const u32x4 *__restrict__ B,
                                                            const uint32_t *__restrict__ amaxA,
                                                            const uint32_t *__restrict__ amaxB, int64_t M, int N,
@@ -629,9 +620,6 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_ntg(const float *__restri
     typedef __attribute__((address_space(3))) void lds_void;
     typedef __attribute__((address_space(1))) void gbl_void;
     auto issue = [&](int kt, int st) {
-        if constexpr (ABL == 1) {
-            if (kt >= 2) return;
-        }
         u32x4 *base = lds + st * STG + w * 64;
 #pragma unroll
         for (int i = 0; i < GA; i++)
@@ -666,7 +654,6 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_ntg(const float *__restri
         u32x4 a[TM][2], b[TN][2];
     };
     auto read = [&](int st, int kh, Frag &f) {
-        if constexpr (ABL == 3) return;
         const u32x4 *sAl = lds + st * STG, *sBl = sAl + BM * 8;
 #pragma unroll
         for (int j = 0; j < TN; j++) {
@@ -680,10 +667,9 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_ntg(const float *__restri
             f.a[i][0] = sAl[r * 8 + (c ^ g_swz(r))];
             f.a[i][1] = sAl[r * 8 + ((c + 1) ^ g_swz(r))];
         }
-    };  // AP: chunk c = 2 g + p is plane p of k chunk g -- the same reads give (h, l)
+    };
     // A's fragments split into planes (in place: a[i][0] = hi plane, a[i][1] = lo plane), then the MFMAs
     auto split = [&](Frag &f) {
-        if constexpr (AP) return;
 #pragma unroll
         for (int i = 0; i < TM; i++) {
             u32x4 ah, al;
@@ -693,14 +679,6 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_ntg(const float *__restri
         }
     };
     auto mfmas = [&](const Frag &f) {
-        if constexpr (ABL >= 2) {
-#pragma unroll
-            for (int i = 0; i < TM; i++) asm volatile("" ::"v"(f.a[i][0]), "v"(f.a[i][1]));
-#pragma unroll
-            for (int j = 0; j < TN; j++) asm volatile("" ::"v"(f.b[j][0]), "v"(f.b[j][1]));
-            return;
-        }
-        if constexpr (PR) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int i = 0; i < TM; i++)
 #pragma unroll
@@ -709,17 +687,10 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_ntg(const float *__restri
                 lo[i][j] = mfma16(f.a[i][0], f.b[j][1], lo[i][j]);
                 hi[i][j] = mfma16(f.a[i][0], f.b[j][0], hi[i][j]);
             }
-        if constexpr (PR) __builtin_amdgcn_s_setprio(0);
     };
     auto mma = [&](Frag &f) {
         split(f);
         mfmas(f);
-    };
-    auto touch = [&](const Frag &f) {
-#pragma unroll
-        for (int i = 0; i < TM; i++) asm volatile("" ::"v"(f.a[i][0]), "v"(f.a[i][1]));
-#pragma unroll
-        for (int j = 0; j < TN; j++) asm volatile("" ::"v"(f.b[j][0]), "v"(f.b[j][1]));
     };
     int st = 0;
     if constexpr (KP) {
@@ -736,24 +707,11 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_ntg(const float *__restri
             const int sn = next(st);
             issue(kt + 2, next(sn));  // the stage read in step kt - 1
             split(f0);
-            if constexpr (ORD) {
-                mfmas(f0);
-                __builtin_amdgcn_sched_barrier(0);
-                read(st, 1, f1);
-            } else {
-                read(st, 1, f1);
-                __builtin_amdgcn_sched_barrier(0);
-                mfmas(f0);
-            }
+            read(st, 1, f1);
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (ORD) {
-                // the compiler's own wait for f1 here (a use of its registers), so it does not add one after the
-                // barrier, where it would also cover the reads of the next half
-                touch(f1);
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G) : "memory");
-            } else {
-                asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(G) : "memory");
-            }
+            mfmas(f0);
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(G) : "memory");
             __builtin_amdgcn_s_barrier();
             split(f1);
             read(sn, 0, f0);
@@ -765,17 +723,10 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_ntg(const float *__restri
         if (kt + 1 < nk) {  // step nk - 2: no DMA left to issue
             const int sn = next(st);
             split(f0);
-            if constexpr (ORD) {
-                mfmas(f0);
-                __builtin_amdgcn_sched_barrier(0);
-                read(st, 1, f1);
-            } else {
-                read(st, 1, f1);
-                __builtin_amdgcn_sched_barrier(0);
-                mfmas(f0);
-            }
+            read(st, 1, f1);
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (ORD) touch(f1);
+            mfmas(f0);
+            __builtin_amdgcn_sched_barrier(0);
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             split(f1);
@@ -1521,7 +1472,7 @@ hipError_t nt_launch(const float *A, const u32x4 *B, const uint32_t *amaxA, cons
     return hipGetLastError();
 }
 
-template <int BM, int BN, int WGM, int WGN, bool KP, bool AP = false, bool PR = false, int ABL = 0, bool ORD = false>
+template <int BM, int BN, int WGM, int WGN, bool KP>
 hipError_t ntg_launch(const float *A, const u32x4 *B, const uint32_t *amaxA, const uint32_t *amaxB, int64_t M, int N,
                       int K, int T, int64_t sA, int64_t sB, const float *bias, float *C, int64_t sC, u32x4 *Pout,
                       hipStream_t s) {
@@ -1532,11 +1483,11 @@ hipError_t ntg_launch(const float *A, const u32x4 *B, const uint32_t *amaxA, con
     if (tiles_m * tiles_n > INT32_MAX) return hipErrorInvalidValue;
     const dim3 grid((unsigned)(tiles_m * tiles_n), T), block(64 * WGM * WGN);
     if (bias)
-        hipLaunchKernelGGL((k_h3_ntg<BM, BN, WGM, WGN, 1, KP, AP, PR, ABL, ORD>), grid, block, 0, s, A, B, amaxA, amaxB,
-                           M, N, K, sA, sB, bias, C, sC, tiles_n);
+        hipLaunchKernelGGL((k_h3_ntg<BM, BN, WGM, WGN, 1, KP>), grid, block, 0, s, A, B, amaxA, amaxB, M, N, K, sA, sB,
+                           bias, C, sC, tiles_n);
     else
-        hipLaunchKernelGGL((k_h3_ntg<BM, BN, WGM, WGN, 0, KP, AP, PR, ABL, ORD>), grid, block, 0, s, A, B, amaxA, amaxB,
-                           M, N, K, sA, sB, nullptr, C, sC, tiles_n);
+        hipLaunchKernelGGL((k_h3_ntg<BM, BN, WGM, WGN, 0, KP>), grid, block, 0, s, A, B, amaxA, amaxB, M, N, K, sA, sB,
+                           nullptr, C, sC, tiles_n);
     return hipGetLastError();
 }
 
@@ -1626,13 +1577,12 @@ hipError_t launch_h3_gemm_nt(const float *A, const uint32_t *amaxA, const void *
 #define H3_NT(BM, BN, WM, WN, PIPE) \
     nt_launch<BM, BN, WM, WN, PIPE>(A, b, amaxA, amaxB, M, N, K, T, a_stride, sB, bias, C, c_stride, P, a_rows, hd, s, \
                                     a_is_planes)
+#define H3_NTG(BM, BN, WM, WN, KP)                         \
+    ((a_rows || head_part) ? hipErrorInvalidValue          \
+                           : ntg_launch<BM, BN, WM, WN, KP>(A, b, amaxA, amaxB, M, N, K, T, a_stride, sB, bias, C, \
+                                                            c_stride, P, s))
     if (a_is_planes && (cfg < 10 || cfg > 14) && cfg != 60) return hipErrorInvalidValue;
-#ifdef MERLIN_PROBES
-    constexpr int PLANE_CFG_END = 80;  // + the probe ablations 70..74
-#else
-    constexpr int PLANE_CFG_END = 70;
-#endif
-    if (cfg >= 60 && cfg < PLANE_CFG_END) {  // both operands as plane images (merlin_h3p.hip)
+    if (cfg >= 60 && cfg < 70) {  // both operands as plane images (merlin_h3p.hip)
         if (P || ((a_rows || head_part) && !a_is_planes)) return hipErrorInvalidValue;
         return launch_h3p_gemm_nt(A, amaxA, B, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, cfg, s, a_rows,
                                   head_w0, n_actions, head_w1, head_part);
@@ -1649,55 +1599,16 @@ hipError_t launch_h3_gemm_nt(const float *A, const uint32_t *amaxA, const void *
         case 12: return H3_NT(128, 128, 2, 2, true);
         case 13: return H3_NT(128, 256, 2, 4, true);
         case 14: return H3_NT(64, 128, 2, 2, true);  // twice cfg 12's blocks (the rollout's 4096-row fc1)
-#undef H3_NT
         // k_h3_ntg: both operands staged by LDS-DMA, three k steps deep
-#define H3_NTG(BM, BN, WM, WN, KP) \
-    ((a_rows || head_part) ? hipErrorInvalidValue                                                  \
-            : ntg_launch<BM, BN, WM, WN, KP>(A, b, amaxA, amaxB, M, N, K, T, a_stride, sB, bias, C, c_stride, P, s))
         case 20: return H3_NTG(256, 128, 4, 2, false);
         case 21: return H3_NTG(128, 192, 4, 2, false);
         // the same with each half step's fragment reads under the previous half step's MFMAs
         case 30: return H3_NTG(256, 128, 4, 2, true);
         case 31: return H3_NTG(128, 192, 4, 2, true);
-#undef H3_NTG
-        // probe (round 5): A as plane images (h3_split of A with amaxA, passed as A), both operands by LDS-DMA
-#define H3_NTGP(BM, BN, WM, WN, KP) \
-    ((a_rows || head_part) ? hipErrorInvalidValue                                                  \
-            : ntg_launch<BM, BN, WM, WN, KP, true>(A, b, amaxA, amaxB, M, N, K, T, a_stride, sB, bias, C, c_stride, P, s))
-        case 40: return H3_NTGP(256, 128, 4, 2, true);
-        case 41: return H3_NTGP(128, 192, 4, 2, true);
-        case 42: return H3_NTGP(128, 256, 2, 4, true);
-        case 43: return H3_NTGP(256, 128, 4, 2, false);
-#undef H3_NTGP
-#define H3_NTGQ(BM, BN, WM, WN, KP) \
-    ((a_rows || head_part) ? hipErrorInvalidValue                                                  \
-            : ntg_launch<BM, BN, WM, WN, KP, true, true>(A, b, amaxA, amaxB, M, N, K, T, a_stride, sB, bias, C, c_stride, P, s))
-        case 44: return H3_NTGQ(128, 256, 2, 4, true);
-        case 45: return H3_NTGQ(256, 128, 4, 2, true);
-        case 46: return H3_NTGQ(256, 128, 4, 2, false);
-#undef H3_NTGQ
-#ifdef MERLIN_PROBES  // ablations (round 5): results are wrong on purpose (no DMA / no MFMA in the k loop)
-#define H3_NTGA(BM, BN, WM, WN, ABL) \
-    ((a_rows || head_part) ? hipErrorInvalidValue                                                  \
-            : ntg_launch<BM, BN, WM, WN, true, true, false, ABL>(A, b, amaxA, amaxB, M, N, K, T, a_stride, sB, bias, C, c_stride, P, s))
-        case 47: return H3_NTGA(128, 256, 2, 4, 1);
-        case 48: return H3_NTGA(128, 256, 2, 4, 2);
-        case 49: return H3_NTGA(128, 256, 2, 4, 3);
-#undef H3_NTGA
-#endif
-#define H3_NTGO(BM, BN, WM, WN, AP, ABL) \
-    ((a_rows || head_part) ? hipErrorInvalidValue                                                  \
-            : ntg_launch<BM, BN, WM, WN, true, AP, false, ABL, true>(A, b, amaxA, amaxB, M, N, K, T, a_stride, sB, bias, C, c_stride, P, s))
-        case 50: return H3_NTGO(128, 256, 2, 4, true, 0);
-        case 51: return H3_NTGO(256, 128, 4, 2, true, 0);
-        case 52: return H3_NTGO(128, 192, 4, 2, true, 0);
-#ifdef MERLIN_PROBES
-        case 53: return H3_NTGO(128, 256, 2, 4, true, 1);  // ablation: no DMA in the main loop
-#endif
-        case 54: return H3_NTGO(128, 256, 2, 4, false, 0);  // fp32 A split at the fragment reads
-#undef H3_NTGO
         default: return hipErrorInvalidValue;
     }
+#undef H3_NT
+#undef H3_NTG
 }
 
 hipError_t launch_h3_gemm_tn(const void *A, const uint32_t *amaxA, const void *B, const uint32_t *amaxB, int64_t Kd,

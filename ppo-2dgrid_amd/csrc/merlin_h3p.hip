@@ -76,7 +76,7 @@ __device__ __forceinline__ void lds_rd(p_u32x4 &d, uint32_t addr) { d = *(const 
 // step add into the same fp32 accumulator: half the accumulator registers, hence twice the tile area per byte staged.
 // Not the same bits as the two-accumulator kernels (a different summation); its error is held to float64 by
 // tests/test_gpu_h3.py like theirs.
-template <int BM, int BN, int WGM, int WGN, int EPI, int NK, int NS = 3, bool ONE = false, int ABL = 0, int ORD = 0>
+template <int BM, int BN, int WGM, int WGN, int EPI, int NK, int NS = 3, bool ONE = false, int ORD = 0>
 __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_pq(const p_u32x4 *__restrict__ A, const p_u32x4 *__restrict__ B,
                                                           const uint32_t *__restrict__ amaxA,
                                                           const uint32_t *__restrict__ amaxB, int64_t M, int N, int K,
@@ -221,8 +221,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_pq(const p_u32x4 *__restr
     static_for<NR>([&](auto K_) __attribute__((always_inline)) { rd(f0, K_, 0, IC<0>{}); });
     static_for<NK>([&](auto KT) __attribute__((always_inline)) {
         constexpr int kt = decltype(KT)::value, st = kt % NS, sn = (kt + 1) % NS;
-        if constexpr (kt + D < NK && !(ABL & 1)) issue(kt + D, (kt + D) % NS);  // the stage read in step kt - 1
-        // (ABL bit 1, a probe: no DMA in the loop -- the MFMA / fragment-read side alone, wrong results)
+        if constexpr (kt + D < NK) issue(kt + D, (kt + D) % NS);  // the stage read in step kt - 1
         __builtin_amdgcn_sched_barrier(0);
         half(f0, f1, (uint32_t)st * STG_B, IC<1>{}, IC<1>{});  // MFMAs of half 0, reads of half 1
         if constexpr (kt + 1 < NK) {
@@ -240,17 +239,6 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_pq(const p_u32x4 *__restr
 
     const float inv = p_pow2(-eA), invB = p_pow2(-eB);
     float *Ct = C + t * sC;
-    if constexpr ((ABL & 2) != 0) {  // probe: no tile stores -- one sum per wave keeps the MFMAs live (wrong results)
-        float sum = 0.0f;
-#pragma unroll
-        for (int i = 0; i < TM; i++)
-#pragma unroll
-            for (int j = 0; j < TN; j++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) sum += hi[i][j][r] + lo[i][j][r];
-        if (lane == 0 && m0 + w < M) Ct[(m0 + w) * N + n0] = sum;
-        return;
-    }
 #pragma unroll
     for (int j = 0; j < TN; j++) {
         const int col = n0 + wn * WTN + j * 32 + fr;
@@ -269,7 +257,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_pq(const p_u32x4 *__restr
     }
 }
 
-template <int BM, int BN, int WGM, int WGN, int NS = 3, bool ONE = false, int ABL = 0, int ORD = 0>
+template <int BM, int BN, int WGM, int WGN, int NS = 3, bool ONE = false, int ORD = 0>
 hipError_t pq_launch(const void *A, const void *B, const uint32_t *amaxA, const uint32_t *amaxB, int64_t M, int N,
                      int K, int T, int64_t sA, int64_t sB, const float *bias, float *C, int64_t sC, hipStream_t s) {
     if (N % BN || K % 32 || K < 64) return hipErrorInvalidValue;
@@ -282,10 +270,10 @@ hipError_t pq_launch(const void *A, const void *B, const uint32_t *amaxA, const 
 #define PQ_K(NK)                                                                                                   \
     do {                                                                                                           \
         if (bias)                                                                                                  \
-            hipLaunchKernelGGL((k_h3_pq<BM, BN, WGM, WGN, 1, NK, NS, ONE, ABL, ORD>), grid, block, 0, s, a, b, amaxA, amaxB, M, N, K, \
+            hipLaunchKernelGGL((k_h3_pq<BM, BN, WGM, WGN, 1, NK, NS, ONE, ORD>), grid, block, 0, s, a, b, amaxA, amaxB, M, N, K, \
                                sA / 4, sB / 4, bias, C, sC, tiles_n);                                              \
         else                                                                                                       \
-            hipLaunchKernelGGL((k_h3_pq<BM, BN, WGM, WGN, 0, NK, NS, ONE, ABL, ORD>), grid, block, 0, s, a, b, amaxA, amaxB, M, N, K, \
+            hipLaunchKernelGGL((k_h3_pq<BM, BN, WGM, WGN, 0, NK, NS, ONE, ORD>), grid, block, 0, s, a, b, amaxA, amaxB, M, N, K, \
                                sA / 4, sB / 4, nullptr, C, sC, tiles_n);                                           \
     } while (0)
     switch (K) {  // the k loop is unrolled: one instantiation per depth (fc1's forward K = 576, input gradient 512)
@@ -834,21 +822,9 @@ hipError_t launch_h3p_gemm_nt(const void *A, const uint32_t *amaxA, const void *
         // waves, 3 stages (144 KB)
         case 65: return pq_launch<256, 192, 4, 2, 2, true>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
         // 66: 62 with the MFMAs product-major (ORD 1: no two consecutive MFMAs on one accumulator; the same bits)
-        case 66: return pq_launch<128, 192, 4, 2, 3, false, 0, 1>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
+        case 66: return pq_launch<128, 192, 4, 2, 3, false, 1>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
         case 68: return pq_launch<256, 256, 2, 2, 2, true>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
         case 69: return pq_launch<192, 192, 3, 2, 3, true>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
-#ifdef MERLIN_PROBES  // ablations (ABL 1: no DMA in the k loop -- wrong results on purpose): 64 = 65's, 67 = 62's, 61 = 66's
-        case 64: return pq_launch<256, 192, 4, 2, 2, true, 1>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
-        case 67: return pq_launch<128, 192, 4, 2, 3, false, 1>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
-        case 61: return pq_launch<128, 192, 4, 2, 3, false, 1, 1>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
-        // ABL 2: no tile stores (the epilogue's share); ABL 3: neither DMA in the loop nor stores -- 70 / 71 = 62's,
-        // 72 / 73 = 60's (the forward's 128 x 256 tile)
-        case 70: return pq_launch<128, 192, 4, 2, 3, false, 2>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
-        case 71: return pq_launch<128, 192, 4, 2, 3, false, 3>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
-        case 72: return pq_launch<128, 256, 2, 4, 3, false, 2>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
-        case 73: return pq_launch<128, 256, 2, 4, 3, false, 3>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
-        case 74: return pq_launch<128, 256, 2, 4, 3, false, 1>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
-#endif
         default: return hipErrorInvalidValue;
     }
 }

@@ -1263,11 +1263,7 @@ def x6_gemm_nt(A: torch.Tensor, B: torch.Tensor, bias: torch.Tensor | None = Non
     B planes int16[T, N, 3K] (x6_split of an f32 [T, N, K])."""
     X6_SPANS.add(name)
     T, M, K = (int(v) for v in A.shape)
-    if A.dtype == torch.int16:  # A as planes too (x6_split of an f32 [T, M, K]): the cfg >= 30 kernels
-        assert cfg >= 30 and K % 24 == 0, "planes A needs an x6 planes-A configuration (cfg >= 30)"
-        K //= 3
-    else:
-        assert A.dtype == torch.float32 and cfg < 30
+    assert A.dtype == torch.float32
     N = int(B.shape[1])
     assert B.dtype == torch.int16 and B.shape == (T, N, 3 * K)
     assert A.is_contiguous() and B.is_contiguous()
@@ -1292,12 +1288,7 @@ def x6_gemm_tn(A: torch.Tensor, B: torch.Tensor, splits: int | None = None, cfg:
     cfg = X6_TN_CFG if cfg is None else cfg
     T, Kd, M = (int(v) for v in A.shape)
     N = int(B.shape[2])
-    if A.dtype == torch.int16:  # both operands as planes (x6_split of f32 [T, Kd, M] / [T, Kd, N]): cfg >= 30
-        assert B.dtype == torch.int16 and cfg >= 30 and M % 24 == 0 and N % 24 == 0
-        M //= 3
-        N //= 3
-    else:
-        assert A.dtype == B.dtype == torch.float32 and cfg < 30
+    assert A.dtype == B.dtype == torch.float32
     assert B.shape[:2] == (T, Kd)
     assert A.is_contiguous() and B.is_contiguous()
     if out is None:
@@ -1427,7 +1418,7 @@ def h3_gemm_nt_planes(Ap: torch.Tensor, amaxA: torch.Tensor, B: torch.Tensor, am
                       bias: torch.Tensor | None = None, cfg: int = 62, out: torch.Tensor | None = None,
                       name: str = "h3_gemm_nt") -> torch.Tensor:
     """h3_gemm_nt with A already in plane form, Ap int16[T, M, 2K] scaled by amaxA's exponent (e.g. head_bwd's dz
-    planes): merlin_h3_gemm_nt_planes, both operands by LDS-DMA (cfg 60 / 61 / 62, K = 512 or 576)."""
+    planes): merlin_h3_gemm_nt_planes, both operands by LDS-DMA (cfg 60 / 62 and the alternates 63 / 65 / 66 / 68 / 69, K = 512 or 576)."""
     H3_SPANS.add(name)
     T, M, K2 = (int(v) for v in Ap.shape)
     K = K2 // 2

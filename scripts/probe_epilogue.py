@@ -1,10 +1,10 @@
-"""Probe (round 6): the plane-operand NT GEMMs' time split into main loop, DMA and epilogue, at the update's shapes
-(input gradient N = 576, K = 512: cfg 62; forward N = 512, K = 576: cfg 60), against the probe-build ablations of
-merlin_h3p.hip k_h3_pq (wrong results on purpose): ABL 1 no DMA in the k loop (67 / 74), ABL 2 no tile stores (70 /
-72), ABL 3 neither (71 / 73).  One block of 144 KB LDS holds a CU, so a tile's prologue (two k steps' DMA) and
+"""Probe (round 6): the plane-operand NT GEMMs' time at the update's shapes (input gradient N = 576, K = 512: cfg 62;
+forward N = 512, K = 576: cfg 60).  The ablations it was written to compare them with (no DMA in the k loop, no tile
+stores, neither: wrong results on purpose) are retired (their numbers:
+profiles/r06ag_epilogue.log).  One block of 144 KB LDS holds a CU, so a tile's prologue (two k steps' DMA) and
 epilogue (its C stores) do not overlap another tile's MFMAs.  HIP-event time per launch, median of 3 alternating
-rounds.  Run with the probe library: make -C ppo-2dgrid_amd -B EXTRA=-DMERLIN_PROBES LIB=lib/libmerlin_hip_probe.so,
-MERLIN_HIP_LIB=ppo-2dgrid_amd/lib/libmerlin_hip_probe.so python scripts/probe_epilogue.py [U] [reps]"""
+rounds.
+    python scripts/probe_epilogue.py [U] [reps]"""
 import os
 import sys
 
@@ -33,8 +33,7 @@ def main():
     # (round 6, profiles/r06ag_epilogue.log: 4-wave blocks on a 2-stage ring, two blocks per CU so that one block's
     # epilogue runs beside the other's MFMAs -- 128 x 128, 256 x 64, 64 x 256 -- took 434 / 468-483 / 464 us, slower
     # than one 8-wave block per CU; those configs were removed again)
-    shapes = {"dgrad": (576, 512, {62: "full", 70: "no stores", 67: "no DMA", 71: "neither"}),
-              "fwd": (512, 576, {60: "full", 72: "no stores", 74: "no DMA", 73: "neither"})}
+    shapes = {"dgrad": (576, 512, {62: "full"}), "fwd": (512, 576, {60: "full"})}
     for name, (N, K, cs) in shapes.items():
         A = torch.relu(torch.randn(2, U, K, device=dev, generator=g))
         B = torch.randn(2, N, K, device=dev, generator=g) / K ** 0.5

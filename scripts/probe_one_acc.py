@@ -1,11 +1,10 @@
 """Probe (round 6): fc1's plane-operand NT GEMMs with ONE accumulator per tile (merlin_h3p.hip k_h3_pq<..., ONE>: the
 lo planes brought back to scale in registers, all three products into one fp32 accumulator) against the
 two-accumulator kernels, at the update's shapes: the input gradient (N = 576, K = 512: cfg 62 vs 65 / 66) and the
-forward's shape (N = 512, K = 576: cfg 60 vs 64 / 67 / 68).  HIP-event time per launch (median of 3 rounds, alternating
+forward's shape (N = 512, K = 576: cfg 60 vs 68).  HIP-event time per launch (median of 3 rounds, alternating
 in one process) and each kernel's error against float64 in the units of tests/test_gpu_h3.py (max |C - C64| /
 sum_k |a_k b_k|), beside torch's fp32 GEMM on the same operands.
-The no-DMA ablations (cfg 61 / 64 / 67) exist only in a -DMERLIN_PROBES build (make -C ppo-2dgrid_amd
-EXTRA=-DMERLIN_PROBES); results: profiles/r06k_one_acc.log, r06r_order.log.
+Results (with the no-DMA ablations since retired): profiles/r06k_one_acc.log, r06r_order.log.
     python scripts/probe_one_acc.py [U] [reps] [cfgs]"""
 import os
 import sys
@@ -39,7 +38,7 @@ def main():
     g = torch.Generator(device=dev).manual_seed(0)
     shapes = {
         # input gradient: dz [U, 512] (sparse-ish, ~1e-6) x W^T -> [U, 576]
-        "dgrad": (576, 512, [62, 66, 67, 61]),
+        "dgrad": (576, 512, [62, 66]),
         # forward's shape: a3 [U, 576] (ReLU output) x W4 [512, 576]^T -> [U, 512]
         "fwd": (512, 576, [60]),
     }

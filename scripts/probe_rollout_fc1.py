@@ -17,7 +17,7 @@ def main():
     a3 = torch.relu(torch.randn(2, n, 576, device=dev, generator=g))
     Wp = nat.x6_split(torch.randn(2, 512, 576, device=dev, generator=g) / 24)
     ref = nat.x6_gemm_nt(a3, Wp, cfg=2)
-    cfgs = [int(c) for c in os.environ.get("CFGS", "2,0,20,25,28,29").split(",")]
+    cfgs = [int(c) for c in os.environ.get("CFGS", "2,0,20,25,28").split(",")]
     times = {c: [] for c in cfgs}
     for c in cfgs:
         err = float((nat.x6_gemm_nt(a3, Wp, cfg=c) - ref).abs().max())

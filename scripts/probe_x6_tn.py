@@ -24,7 +24,7 @@ def ev_time(fn, reps=5):
 def main():
     U = int(sys.argv[1]) if len(sys.argv) > 1 else 116192
     rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 7
-    combos = [tuple(int(v) for v in c.split(":")) for c in os.environ.get("COMBOS", "0:32,20:32,30:32,30:16").split(",")]
+    combos = [tuple(int(v) for v in c.split(":")) for c in os.environ.get("COMBOS", "0:32,20:32,24:32,20:16").split(",")]
     dev = torch.device("cuda")
     g = torch.Generator(device=dev).manual_seed(0)
     a3 = torch.relu(torch.randn(2, U, 576, device=dev, generator=g))
@@ -33,19 +33,17 @@ def main():
     W64 = torch.bmm(dz.double().transpose(1, 2), a3.double())
     rel = lambda W: float((W.double() - W64).norm() / W64.norm())  # noqa: E731
     print(f"hipBLASLt fp32 rel err {rel(torch.bmm(dz.transpose(1, 2), a3)):.3e}", flush=True)
-    dzp, a3p = nat.x6_split(dz), nat.x6_split(a3)  # planes operands for the cfg >= 30 kernels
-    ops = lambda c: (dzp, a3p) if c >= 30 else (dz, a3)  # noqa: E731
     ok = {}
     for c, s in combos:
         try:
-            W = nat.x6_gemm_tn(*ops(c), splits=s, cfg=c)
-            ok[(c, s)] = (rel(W), bool(torch.equal(W, nat.x6_gemm_tn(*ops(c), splits=s, cfg=c))))
+            W = nat.x6_gemm_tn(dz, a3, splits=s, cfg=c)
+            ok[(c, s)] = (rel(W), bool(torch.equal(W, nat.x6_gemm_tn(dz, a3, splits=s, cfg=c))))
         except nat.MerlinNativeError as ex:
             print(c, s, ex)
     times = {k: [] for k in ok}
     for _ in range(rounds):
         for c, s in ok:
-            times[(c, s)].append(ev_time(lambda: nat.x6_gemm_tn(*ops(c), splits=s, cfg=c)))
+            times[(c, s)].append(ev_time(lambda: nat.x6_gemm_tn(dz, a3, splits=s, cfg=c)))
     ex = 6 * 2 * 2 * U * 512 * 576
     for k in ok:
         med = statistics.median(times[k])

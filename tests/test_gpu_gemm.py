@@ -119,3 +119,36 @@ def test_window_update_x6_matches_hipblaslt(device, impl):
         g1, g2 = grads[impl][k], grads["hipblaslt"][k]
         scale = float(g2.abs().max()) + 1e-12
         assert float((g1 - g2).abs().max()) <= 2e-5 * scale, k
+
+
+@pytest.mark.parametrize("kind,cfg", [("nt", 4), ("nt", 10), ("nt", 17), ("nt", 29), ("nt", 30), ("tn", 30)])
+def test_retired_cfg_refused(device, kind, cfg):
+    """The retired x6 configurations (NT: unchunked 4, interleaved staging 10..17, 64 x 128 tiles 29, A as planes
+    30 / 32; TN: both operands as planes 30) are host-side refusals -- E_UNSUPPORTED, nothing launched -- and a valid
+    call behind the refusal on the same stream gives the same, right result."""
+    from merlin import _native as nat
+
+    g = torch.Generator(device=device).manual_seed(cfg)
+    if kind == "nt":  # one tower, M = 1, N = 256, K = 64
+        A = torch.relu(torch.randn(1, 1, 64, device=device, generator=g))
+        B = torch.randn(1, 256, 64, device=device, generator=g) / 8
+        Bp = nat.x6_split(B)
+        ref64, ref32 = torch.bmm(A.double(), B.double().transpose(1, 2)), torch.bmm(A, B.transpose(1, 2))
+        den = torch.bmm(A.abs().double(), B.abs().double().transpose(1, 2))
+        run = lambda c, out=None: nat.x6_gemm_nt(A, Bp, cfg=c, out=out)  # noqa: E731
+        good = 2
+    else:  # one tower, Kd = 64, one 128 x 192 tile
+        A = torch.randn(1, 64, 128, device=device, generator=g)
+        B = torch.relu(torch.randn(1, 64, 192, device=device, generator=g))
+        ref64, ref32 = torch.bmm(A.double().transpose(1, 2), B.double()), torch.bmm(A.transpose(1, 2), B)
+        den = torch.bmm(A.abs().double().transpose(1, 2), B.abs().double())
+        run = lambda c, out=None: nat.x6_gemm_tn(A, B, splits=1, cfg=c, out=out)  # noqa: E731
+        good = 0
+    before = run(good)
+    assert _err(before, ref64, den) <= max(2 * _err(ref32, ref64, den), TOL_FLOOR)
+    out = torch.full_like(before, -7.0)
+    with pytest.raises(nat.MerlinNativeError) as ei:
+        run(cfg, out)
+    assert ei.value.code == nat.E_UNSUPPORTED
+    assert bool((out == -7.0).all())
+    assert torch.equal(run(good, out), before)

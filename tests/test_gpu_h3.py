@@ -280,3 +280,53 @@ def test_gemm_nt_planes_vs_float64(device, M, N, K, cfg, scale_a, ragged):
     assert torch.equal(C, nat.h3_gemm_nt_planes(Ap, amA, Bp, amB, cfg=cfg))  # fixed order: the same bits every call
     if cfg in (63, 66):
         assert torch.equal(C, nat.h3_gemm_nt_planes(Ap, amA, Bp, amB, cfg=62))
+
+
+def _refused(call, out):
+    """A retired configuration number is a host-side refusal: E_UNSUPPORTED, and nothing written to `out`."""
+    from merlin import _native as nat
+
+    out.fill_(-7.0)
+    with pytest.raises(nat.MerlinNativeError) as ei:
+        call()
+    assert ei.value.code == nat.E_UNSUPPORTED
+    assert bool((out == -7.0).all())
+
+
+@pytest.mark.parametrize("cfg", [40, 42, 46, 47, 50, 54])
+def test_gemm_nt_retired_cfg_refused(device, cfg):
+    """The retired k_h3_ntg variants (A as planes 40..46, ablations 47..49, reordered half steps 50..54) are refused
+    without a launch, and a valid call behind the refusal on the same stream gives the same, right result."""
+    from merlin import _native as nat
+
+    A, B = _operands(device, 1, 256, 64, 5)
+    A, B = A[:1].contiguous(), B[:1].contiguous()  # one tower
+    C64 = torch.bmm(A.double(), B.double().transpose(1, 2))
+    den = torch.bmm(A.abs().double(), B.abs().double().transpose(1, 2))
+    tol = max(_err(torch.bmm(A, B.transpose(1, 2)), C64, den), FLOOR)
+    amA, amB = nat.h3_amax(A), nat.h3_amax(B)
+    Bp = nat.h3_split(B, amB)
+    before = nat.h3_gemm_nt(A, amA, Bp, amB, cfg=2)
+    assert _err(before, C64, den) <= tol
+    out = torch.empty_like(before)
+    _refused(lambda: nat.h3_gemm_nt(A, amA, Bp, amB, cfg=cfg, out=out), out)
+    assert torch.equal(nat.h3_gemm_nt(A, amA, Bp, amB, cfg=2, out=out), before)
+
+
+@pytest.mark.parametrize("cfg", [61, 64, 67, 70, 74])
+def test_gemm_nt_planes_retired_cfg_refused(device, cfg):
+    """The retired k_h3_pq ablations (61 / 64 / 67 inside the plane range, 70..74 above it) are refused likewise."""
+    from merlin import _native as nat
+
+    A, B = _operands(device, 1, 576, 512, 6)
+    A, B = A[:1].contiguous(), B[:1].contiguous()
+    C64 = torch.bmm(A.double(), B.double().transpose(1, 2))
+    den = torch.bmm(A.abs().double(), B.abs().double().transpose(1, 2))
+    tol = max(_err(torch.bmm(A, B.transpose(1, 2)), C64, den), FLOOR)
+    amA, amB = nat.h3_amax(A), nat.h3_amax(B)
+    Ap, Bp = nat.h3_split(A, amA), nat.h3_split(B, amB)
+    before = nat.h3_gemm_nt_planes(Ap, amA, Bp, amB, cfg=62)
+    assert _err(before, C64, den) <= tol
+    out = torch.empty_like(before)
+    _refused(lambda: nat.h3_gemm_nt_planes(Ap, amA, Bp, amB, cfg=cfg, out=out), out)
+    assert torch.equal(nat.h3_gemm_nt_planes(Ap, amA, Bp, amB, cfg=62, out=out), before)
