@@ -702,9 +702,15 @@ int merlin_h3_gemm_nt_heads(const float *A_dev, const uint32_t *amax_a_dev, cons
                             const int32_t *a_rows_dev, const float *head_w0_dev, int32_t n_actions,
                             const float *head_w1_dev, float *head_partials_dev, int32_t cfg, void *stream);
 int32_t merlin_h3_heads_parts(int32_t N, int32_t cfg);
+/* h3_walk_blocks: the persistent plane-operand NT kernels (gemm_nt_planes cfg 62 / 78, gemm_nt_heads_planes cfg 60 /
+ *          76: one block per CU walking a static list of tiles; 77 / 75 are the same kernels with a block per tile,
+ *          the same bits) launch `blocks` blocks instead of one per CU until set back to 0.  Process-wide, for tests
+ *          of the walk that must not depend on the device's CU count; never more blocks than tiles are launched. */
+int merlin_h3_walk_blocks(int32_t blocks);
 /* gemm_nt_planes: gemm_nt with A already in plane form too (A_planes [t][M][K/8][2][8] f16 scaled by amax_a_dev's
  *          exponent, e.g. merlin_tower_head_bwd_planes' dz), both operands staged into LDS by DMA (csrc/merlin_h3p.hip):
- *          cfg 60 128x256 / 62 128x192 tiles, K = 512 or 576, bias as gemm_nt.  Same products and order as gemm_nt
+ *          cfg 60 128x256 / 62 128x192 tiles (62: the persistent kernel, a block per CU walking tiles, also 78; 77:
+ *          the same tile with a block per tile, the same bits), K = 512 or 576, bias as gemm_nt.  Same products and order as gemm_nt
  *          on the fp32 A with the same scale: the same bits.  Measured alternates (round 6, not on the benched path):
  *          63 = 62 on a 4-stage ring; 66 = 62 with its MFMAs product-major (the same bits); 65 / 68 / 69 = one
  *          accumulator per tile (the lo planes rescaled in registers: another summation, held to float64 like the

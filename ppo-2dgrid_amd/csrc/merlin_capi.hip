@@ -1318,7 +1318,8 @@ int merlin_h3_gemm_nt(const float *A, const uint32_t *amax_a, const void *B, con
 int merlin_h3_gemm_nt_planes(const void *A_planes, const uint32_t *amax_a, const void *B, const uint32_t *amax_b,
                              int64_t M, int32_t N, int32_t K, int32_t towers, int64_t a_stride, int64_t b_stride,
                              const float *bias, float *C, int64_t c_stride, int32_t cfg, void *stream) {
-    if (cfg < 60 || cfg >= 70) return fail(MERLIN_E_UNSUPPORTED, "plane-operand cfgs are 60..69");
+    if (cfg < 60 || (cfg >= 70 && cfg != 77 && cfg != 78))
+        return fail(MERLIN_E_UNSUPPORTED, "plane-operand cfgs are 60..69, 77 and 78");
     return h3_gemm_nt(static_cast<const float *>(A_planes), amax_a, B, amax_b, M, N, K, towers, a_stride, b_stride,
                       bias, C, c_stride, nullptr, nullptr, cfg, stream);
 }
@@ -1370,6 +1371,12 @@ int merlin_h3_gemm_nt_heads(const float *A, const uint32_t *amax_a, const void *
 }
 
 int32_t merlin_h3_heads_parts(int32_t N, int32_t cfg) { return merlin::h3_heads_parts(N, cfg); }
+
+int merlin_h3_walk_blocks(int32_t blocks) {
+    if (blocks < 0) return fail(MERLIN_E_INVALID, "blocks must be 0 (one per CU) or positive");
+    merlin::set_h3p_walk_blocks(blocks);
+    return MERLIN_OK;
+}
 
 int merlin_act_draw(const float *partials, int32_t parts, int64_t n, const float *b_actor, const float *b_critic,
                     int32_t n_actions, int32_t deterministic, uint64_t seed, const int64_t *epoch, int64_t step,

@@ -1581,8 +1581,8 @@ hipError_t launch_h3_gemm_nt(const float *A, const uint32_t *amaxA, const void *
     ((a_rows || head_part) ? hipErrorInvalidValue          \
                            : ntg_launch<BM, BN, WM, WN, KP>(A, b, amaxA, amaxB, M, N, K, T, a_stride, sB, bias, C, \
                                                             c_stride, P, s))
-    if (a_is_planes && (cfg < 10 || cfg > 14) && cfg != 60) return hipErrorInvalidValue;
-    if (cfg >= 60 && cfg < 70) {  // both operands as plane images (merlin_h3p.hip)
+    if (a_is_planes && (cfg < 10 || cfg > 14) && cfg != 60 && cfg != 75 && cfg != 76) return hipErrorInvalidValue;
+    if ((cfg >= 60 && cfg < 70) || (cfg >= 75 && cfg < 79)) {  // both operands as plane images (merlin_h3p.hip)
         if (P || ((a_rows || head_part) && !a_is_planes)) return hipErrorInvalidValue;
         return launch_h3p_gemm_nt(A, amaxA, B, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, cfg, s, a_rows,
                                   head_w0, n_actions, head_w1, head_part);
@@ -1686,7 +1686,9 @@ int h3_heads_parts(int N, int cfg) {
         case 12: return N % 128 ? 0 : N / 128 * 2;
         case 13: return N % 256 ? 0 : N / 256 * 4;
         case 14: return N % 128 ? 0 : N / 128 * 2;
-        case 60: return N % 256 ? 0 : N / 256 * 4;  // k_h3_pqg (planes, gathered rows): cfg 13's tiles
+        case 60:  // k_h3_pqg (planes, gathered rows): cfg 13's tiles; 75 / 76 its one-tile and persistent forms
+        case 75:
+        case 76: return N % 256 ? 0 : N / 256 * 4;
         default: return 0;
     }
 }

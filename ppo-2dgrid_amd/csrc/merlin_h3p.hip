@@ -76,12 +76,14 @@ __device__ __forceinline__ void lds_rd(p_u32x4 &d, uint32_t addr) { d = *(const 
 // step add into the same fp32 accumulator: half the accumulator registers, hence twice the tile area per byte staged.
 // Not the same bits as the two-accumulator kernels (a different summation); its error is held to float64 by
 // tests/test_gpu_h3.py like theirs.
-template <int BM, int BN, int WGM, int WGN, int EPI, int NK, int NS = 3, bool ONE = false, int ORD = 0>
-__global__ __launch_bounds__(64 * WGM * WGN) void k_h3_pq(const p_u32x4 *__restrict__ A, const p_u32x4 *__restrict__ B,
-                                                          const uint32_t *__restrict__ amaxA,
-                                                          const uint32_t *__restrict__ amaxB, int64_t M, int N, int K,
-                                                          int64_t sA, int64_t sB, const float *__restrict__ bias,
-                                                          float *__restrict__ C, int64_t sC, int tiles_n) {
+// (pq_tile: the body of k_h3_pq's one-tile form, a block per tile; the kernel and its persistent form are defined
+// behind the walks, at the end of this namespace)
+template <int BM, int BN, int WGM, int WGN, int EPI, int NK, int NS, bool ONE, int ORD>
+__device__ __forceinline__ void pq_tile(const p_u32x4 *__restrict__ A, const p_u32x4 *__restrict__ B,
+                                        const uint32_t *__restrict__ amaxA, const uint32_t *__restrict__ amaxB,
+                                        int64_t M, int N, int K, int64_t sA, int64_t sB,
+                                        const float *__restrict__ bias, float *__restrict__ C, int64_t sC,
+                                        int tiles_n) {
     constexpr int NT = 64 * WGM * WGN;
     constexpr int WTM = BM / WGM, WTN = BN / WGN;
     constexpr int TM = WTM / 32, TN = WTN / 32;
@@ -256,35 +258,6 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_pq(const p_u32x4 *__restr
         }
     }
 }
-
-template <int BM, int BN, int WGM, int WGN, int NS = 3, bool ONE = false, int ORD = 0>
-hipError_t pq_launch(const void *A, const void *B, const uint32_t *amaxA, const uint32_t *amaxB, int64_t M, int N,
-                     int K, int T, int64_t sA, int64_t sB, const float *bias, float *C, int64_t sC, hipStream_t s) {
-    if (N % BN || K % 32 || K < 64) return hipErrorInvalidValue;
-    const int64_t tiles_m = (M + BM - 1) / BM;
-    const int tiles_n = N / BN;
-    if (tiles_m * tiles_n > INT32_MAX) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)(tiles_m * tiles_n), T), block(64 * WGM * WGN);
-    const auto *a = static_cast<const p_u32x4 *>(A);
-    const auto *b = static_cast<const p_u32x4 *>(B);
-#define PQ_K(NK)                                                                                                   \
-    do {                                                                                                           \
-        if (bias)                                                                                                  \
-            hipLaunchKernelGGL((k_h3_pq<BM, BN, WGM, WGN, 1, NK, NS, ONE, ORD>), grid, block, 0, s, a, b, amaxA, amaxB, M, N, K, \
-                               sA / 4, sB / 4, bias, C, sC, tiles_n);                                              \
-        else                                                                                                       \
-            hipLaunchKernelGGL((k_h3_pq<BM, BN, WGM, WGN, 0, NK, NS, ONE, ORD>), grid, block, 0, s, a, b, amaxA, amaxB, M, N, K, \
-                               sA / 4, sB / 4, nullptr, C, sC, tiles_n);                                           \
-    } while (0)
-    switch (K) {  // the k loop is unrolled: one instantiation per depth (fc1's forward K = 576, input gradient 512)
-        case 576: PQ_K(18); break;
-        case 512: PQ_K(16); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef PQ_K
-    return hipGetLastError();
-}
-
 
 // ---------------------------------------------------------------------------------------------------------------
 // TN over plane operands with LDS-DMA staging (round 5; the weight gradient dz^T a3, merlin_h3_gemm_tn_gather_planes
@@ -549,15 +522,14 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tq(const p_u32x4 *__restr
 // heads' partial dot products, merlin_heads_combine's layout).  The block's 9 BM chunk rows are read into LDS once;
 // a step's A sources are read from there one step ahead.  DMAs by inline asm as in k_h3_tq (no compiler-inserted
 // vmcnt before LDS reads).  The same products in the same order as k_h3_ntpg: the same bits.
+// (pqg_tile: the body of k_h3_pqg's one-tile form)
 template <int BM, int BN, int WGM, int WGN, int EPI>
-__global__ __launch_bounds__(64 * WGM * WGN) void k_h3_pqg(const p_u32x4 *__restrict__ A, const p_u32x4 *__restrict__ B,
-                                                           const uint32_t *__restrict__ amaxA,
-                                                           const uint32_t *__restrict__ amaxB, int64_t M, int N,
-                                                           int64_t sA, int64_t sB, const float *__restrict__ bias,
-                                                           float *__restrict__ C, int64_t sC, int tiles_n,
-                                                           const int32_t *__restrict__ amap,
-                                                           const float *__restrict__ hw0, const float *__restrict__ hw1,
-                                                           int na, float *__restrict__ hpart) {
+__device__ __forceinline__ void pqg_tile(const p_u32x4 *__restrict__ A, const p_u32x4 *__restrict__ B,
+                                         const uint32_t *__restrict__ amaxA, const uint32_t *__restrict__ amaxB,
+                                         int64_t M, int N, int64_t sA, int64_t sB, const float *__restrict__ bias,
+                                         float *__restrict__ C, int64_t sC, int tiles_n,
+                                         const int32_t *__restrict__ amap, const float *__restrict__ hw0,
+                                         const float *__restrict__ hw1, int na, float *__restrict__ hpart) {
     constexpr int K = 576, NK = 18, KC = K / 64;
     constexpr int NT = 64 * WGM * WGN;
     constexpr int WTM = BM / WGM, WTN = BN / WGN;
@@ -784,10 +756,683 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_pqg(const p_u32x4 *__rest
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Persistent forms of the two NT kernels above (k_h3_pq / k_h3_pqg with PERS): at most one block per CU, each
+// walking a static list of (tower, tile) items -- item p_xcd_tile(b + i gridDim.x, T x tiles) of the tower-major
+// list for block b's i-th tile, so the blocks of one XCD still work on neighbouring tiles at the same time.  No
+// block talks to another: no counters, nothing to spin on.
+// The DMA ring runs on across tile boundaries: the last two k steps of a tile issue the first two of the block's
+// next tile (the block's last tile fetches its own first steps again, so that every count below is static; they
+// are drained before the block ends), then the tile's C stores go out, then step 2 of the next tile is issued.
+// vmcnt retires in issue order, so the wait for step 1 (issued before the stores) lets the stores and step 2 stay
+// in flight; the wait for step 2, a k step later, is the first that needs the stores gone.  The stores' count
+// must be exact for that, so only a tile whose rows all exist stores unconditionally and carries them into the
+// next tile; a ragged tile stores under its row test and drains (one tile in ~900).
+// Scales, bias and head weights are plain loads, and hipcc's own wait for a plain load also waits for every DMA
+// issued before it: they are loaded before the first DMA and again only when the tower / column tile of the item
+// changes (with an explicit drain).  Per output element the same products in the same order and the same epilogue
+// arithmetic as the one-tile forms: the same bits.
+#define P_VMCNT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
+// DMA with a uniform 64-bit base and a 32-bit byte offset per lane (no immediate: the instruction's offset field moves
+// the LDS address as well as the global one, so a k step's 128 B x kt goes into the base by scalar adds)
+__device__ __forceinline__ void p_dma16s(const void *sbase, uint32_t voff, uint32_t lds) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(voff), "s"(sbase), "s"(lds)
+                 : "memory");
+}
+__device__ __forceinline__ void p_dma4s(const void *sbase, uint32_t voff, uint32_t lds) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(voff), "s"(sbase), "s"(lds)
+                 : "memory");
+}
+// every counter but vmcnt left alone (gfx9 encoding: vmcnt 0, expcnt 7, lgkmcnt 15): a wait the compiler sees
+__device__ __forceinline__ void p_drain_loads() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+
+struct PItem {
+    int t, n0, tn;
+    int64_t m0;
+};
+__device__ __forceinline__ PItem p_item(int v, int W, int tiles, int tiles_n, int BM, int BN) {
+    const int it = p_xcd_tile(v, W), t = it / tiles, L = it - t * tiles, tm = L / tiles_n, tn = L - tm * tiles_n;
+    return PItem{t, tn * BN, tn, (int64_t)tm * BM};
+}
+
+template <int BM, int BN, int WGM, int WGN, int EPI, int NK, int ORD>
+__device__ __forceinline__ void pq_walk(const p_u32x4 *__restrict__ A, const p_u32x4 *__restrict__ B,
+                                        const uint32_t *__restrict__ amaxA, const uint32_t *__restrict__ amaxB,
+                                        int64_t M, int N, int K, int64_t sA, int64_t sB,
+                                        const float *__restrict__ bias, float *__restrict__ C, int64_t sC,
+                                        int tiles_n, int tiles, int W) {
+    constexpr int NT = 64 * WGM * WGN;
+    constexpr int WTM = BM / WGM, WTN = BN / WGN;
+    constexpr int TM = WTM / 32, TN = WTN / 32;
+    constexpr int NR = 2 * (TM + TN), NM = 3 * TM * TN;
+    static_assert(NM >= NR, "a read behind every MFMA");
+    static_assert((BM * 8) % NT == 0 && (BN * 8) % NT == 0, "whole DMA instructions per thread");
+    constexpr int GA = BM * 8 / NT, GB = BN * 8 / NT, G = GA + GB;
+    constexpr int STG = (BM + BN) * 8;
+    constexpr uint32_t STG_B = STG * 16;
+    constexpr int S = TM * TN * 16;               // C stores per wave and tile
+    constexpr int CARRY = S + G < 63 ? S + G : 63;  // the vmcnt field's largest value
+    const int N_ = N;
+    static_assert(NK >= 4, "the look-ahead's k steps");
+    __shared__ p_u32x4 lds[3 * STG];
+
+    int v = blockIdx.x;
+    const int nb = gridDim.x;
+    if (v >= W) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int wm = w / WGN, wn = w - (w / WGN) * WGN;
+    const int64_t row_ch = K / 4;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) p_u32x4 *)lds;
+    const uint32_t wbase = (uint32_t)__builtin_amdgcn_readfirstlane(w) * 64u * 16u;
+
+    PItem cur = p_item(v, W, tiles, tiles_n, BM, BN);
+    // the epilogue's constants of the item they were loaded for
+    int lt = cur.t, ln = cur.n0;
+    int eA = p_exp(p_amax(amaxA + lt)), eB = p_exp(p_amax(amaxB + lt));
+    float bvv[TN];
+    const int fr = lane & 31, fh = lane >> 5;
+#pragma unroll
+    for (int j = 0; j < TN; j++) bvv[j] = EPI == 1 ? bias[(int64_t)lt * N + ln + wn * WTN + j * 32 + fr] : 0.0f;
+    p_drain_loads();
+
+    uint32_t offA[GA], offB[GB];  // byte offsets from the item's uniform row-block bases
+    auto set_offA = [&](const PItem &it) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < GA; i++) {
+            const int q = i * NT + tid, r = q >> 3, c = (q & 7) ^ p_swz(r);
+            offA[i] = (uint32_t)(std::min<int64_t>(r, M - 1 - it.m0) * row_ch + c) * 16u;
+        }
+    };
+#pragma unroll
+    for (int i = 0; i < GB; i++) {
+        const int q = (GA + i) * NT + tid, r = q >> 3, c = (q & 7) ^ p_swz(r);
+        offB[i] = (uint32_t)((r - BM) * row_ch + c) * 16u;
+    }
+    const p_u32x4 *bA, *bB;  // the item the DMAs are issued for
+    auto set_base = [&](const PItem &it) __attribute__((always_inline)) {
+        bA = A + it.t * sA + it.m0 * row_ch;
+        bB = B + it.t * sB + (int64_t)it.n0 * row_ch;
+        set_offA(it);
+    };
+    // logical stage s (k step kt's is kt % 3) -> byte offset of the physical stage: NK % 3 stages on per tile
+    uint32_t sv[3] = {0u, STG_B, 2u * STG_B};
+    auto issue = [&](auto KT, uint32_t so) __attribute__((always_inline)) {
+        constexpr int kt = decltype(KT)::value;
+        const uint32_t base = lds0 + so + wbase;
+#pragma unroll
+        for (int i = 0; i < GA; i++) p_dma16s(bA + kt * 8, offA[i], base + (uint32_t)(i * NT) * 16u);
+#pragma unroll
+        for (int i = 0; i < GB; i++) p_dma16s(bB + kt * 8, offB[i], base + (uint32_t)((GA + i) * NT) * 16u);
+    };
+
+    uint32_t adA[2][2], adB[2][2];
+    {
+        const int ra = wm * WTM + fr, rb = BM + wn * WTN + fr;
+#pragma unroll
+        for (int kh = 0; kh < 2; kh++)
+#pragma unroll
+            for (int p = 0; p < 2; p++) {
+                const int c = 2 * (2 * kh + fh) + p;
+                adA[kh][p] = lds0 + (uint32_t)(ra * 8 + (c ^ p_swz(ra))) * 16u;
+                adB[kh][p] = lds0 + (uint32_t)(rb * 8 + (c ^ p_swz(rb))) * 16u;
+            }
+    }
+    struct Frag {
+        p_u32x4 a[TM][2], b[TN][2];
+    };
+    p_f32x16 hi[TM][TN], lo[TM][TN];
+    auto zero = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < TM; i++)
+#pragma unroll
+            for (int j = 0; j < TN; j++) {
+                hi[i][j] = p_f32x16{};
+                lo[i][j] = p_f32x16{};
+            }
+    };
+    zero();
+    auto rd = [&](Frag &g, auto K_, uint32_t so, auto KH) __attribute__((always_inline)) {
+        constexpr int k = decltype(K_)::value, kh = decltype(KH)::value;
+        if constexpr (k < 2 * TM)
+            lds_rd(g.a[k >> 1][k & 1], adA[kh][k & 1] + so + (k >> 1) * 32 * 128);
+        else
+            lds_rd(g.b[(k - 2 * TM) >> 1][k & 1], adB[kh][k & 1] + so + ((k - 2 * TM) >> 1) * 32 * 128);
+    };
+    auto mf = [&](const Frag &f, auto M_) __attribute__((always_inline)) {  // k_h3_pq's orders
+        constexpr int m = decltype(M_)::value, tl = ORD ? m % (TM * TN) : m / 3, pr = ORD ? m / (TM * TN) : m % 3;
+        constexpr int i = tl / TN, j = tl % TN;
+        if constexpr (pr == 0)
+            lo[i][j] = p_mfma(f.a[i][1], f.b[j][0], lo[i][j]);
+        else if constexpr (pr == 1)
+            lo[i][j] = p_mfma(f.a[i][0], f.b[j][1], lo[i][j]);
+        else
+            hi[i][j] = p_mfma(f.a[i][0], f.b[j][0], hi[i][j]);
+    };
+    auto half = [&](const Frag &f, Frag &g, uint32_t so, auto KH, auto READS) __attribute__((always_inline)) {
+        static_for<NM>([&](auto M_) __attribute__((always_inline)) {
+            mf(f, M_);
+            if constexpr (decltype(READS)::value && decltype(M_)::value < NR) rd(g, M_, so, KH);
+        });
+        if constexpr (decltype(READS)::value) {
+            static_for<NR>([&](auto) __attribute__((always_inline)) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            });
+            if constexpr (NM > NR) __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto touch = [&](const Frag &f) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < TM; i++) asm volatile("" ::"v"(f.a[i][0]), "v"(f.a[i][1]));
+#pragma unroll
+        for (int j = 0; j < TN; j++) asm volatile("" ::"v"(f.b[j][0]), "v"(f.b[j][1]));
+    };
+    auto publish = [&]() __attribute__((always_inline)) {
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto store_tile = [&](auto FULL) __attribute__((always_inline)) {
+        const float inv = p_pow2(-eA), invB = p_pow2(-eB);
+        float *Ct = C + cur.t * sC;
+        // opaque per tile: the 48 store addresses are made here, not hoisted out of the walk and kept (or spilled)
+        int64_t N = N_;
+        int rw = wm * WTM + 4 * fh;
+        asm volatile("" : "+s"(N), "+v"(rw));
+#pragma unroll
+        for (int j = 0; j < TN; j++) {
+            const int col = cur.n0 + wn * WTN + j * 32 + fr;
+#pragma unroll
+            for (int i = 0; i < TM; i++) {
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int64_t row = cur.m0 + rw + i * 32 + (r & 3) + 8 * (r >> 2);
+                    if (decltype(FULL)::value || row < M) {
+                        const float x = (hi[i][j][r] + lo[i][j][r] * P_LO_INV) * inv * invB;
+                        Ct[row * N + col] = EPI == 1 ? p_relu(x + bvv[j]) : x;
+                    }
+                }
+            }
+        }
+    };
+
+    set_base(cur);
+    issue(IC<0>{}, sv[0]);
+    issue(IC<1>{}, sv[1]);
+    P_VMCNT(G);  // step 0 landed
+    publish();
+    bool carried = false;  // the previous tile's C stores may still be in flight
+    for (;;) {
+        const bool more = v + nb < W;
+        const PItem nxt = more ? p_item(v + nb, W, tiles, tiles_n, BM, BN) : cur;
+        Frag f0, f1;
+        static_for<NR>([&](auto K_) __attribute__((always_inline)) { rd(f0, K_, sv[0], IC<0>{}); });
+        static_for<NK>([&](auto KT) __attribute__((always_inline)) {
+            constexpr int kt = decltype(KT)::value, st = kt % 3, sn = (kt + 1) % 3, s2 = (kt + 2) % 3;
+            if constexpr (kt == NK - 2) set_base(nxt);  // from here on the DMAs are the next item's
+            issue(IC<(kt + 2) % NK>{}, sv[s2]);         // the stage read in step kt - 1
+            __builtin_amdgcn_sched_barrier(0);
+            half(f0, f1, sv[st], IC<1>{}, IC<1>{});
+            touch(f1);
+            // step kt + 1 landed: the step just issued may stay in flight, and behind the first step of a tile the
+            // stores of the tile before it, which were issued between the two
+            if constexpr (kt == 0) {
+                if (carried)
+                    P_VMCNT(CARRY);
+                else
+                    P_VMCNT(G);
+            } else {
+                P_VMCNT(G);
+            }
+            publish();  // step kt + 1 published; every wave is past its reads of step kt - 1
+            if constexpr (kt + 1 < NK)
+                half(f1, f0, sv[sn], IC<0>{}, IC<1>{});
+            else
+                half(f1, f0, 0u, IC<0>{}, IC<0>{});
+        });
+        if (cur.t != lt || (EPI == 1 && cur.n0 != ln)) {
+            lt = cur.t, ln = cur.n0;
+            eA = p_exp(p_amax(amaxA + lt)), eB = p_exp(p_amax(amaxB + lt));
+#pragma unroll
+            for (int j = 0; j < TN; j++)
+                bvv[j] = EPI == 1 ? bias[(int64_t)lt * N + ln + wn * WTN + j * 32 + fr] : 0.0f;
+            p_drain_loads();
+        }
+        carried = cur.m0 + BM <= M;
+        if (carried) {
+            store_tile(IC<1>{});
+        } else {
+            store_tile(IC<0>{});
+            P_VMCNT(0);
+        }
+        zero();
+        if (!more) break;
+        v += nb;
+        cur = nxt;
+        if constexpr (NK % 3 == 1) {
+            const uint32_t x = sv[0];
+            sv[0] = sv[1], sv[1] = sv[2], sv[2] = x;
+        } else if constexpr (NK % 3 == 2) {
+            const uint32_t x = sv[2];
+            sv[2] = sv[1], sv[1] = sv[0], sv[0] = x;
+        }
+    }
+    P_VMCNT(0);  // the last tile's look-ahead DMAs: landed before the block's LDS is given away
+}
+
+// k_h3_pqg's walk (K = 576: 18 k steps, the ring's stages line up from tile to tile).  The row map of a tile
+// (BM x 9 chunk rows) is itself fetched by DMA, into the other of two LDS buffers, in the middle of the tile before:
+// three 4-byte DMAs per thread behind step 10's data, which the waits of steps 8 and 9 let stay in flight.
+template <int BM, int BN, int WGM, int WGN, int EPI>
+__device__ __forceinline__ void pqg_walk(const p_u32x4 *__restrict__ A, const p_u32x4 *__restrict__ B,
+                                         const uint32_t *__restrict__ amaxA, const uint32_t *__restrict__ amaxB,
+                                         int64_t M, int N, int64_t sA, int64_t sB, const float *__restrict__ bias,
+                                         float *__restrict__ C, int64_t sC, int tiles_n, int tiles, int W,
+                                         const int32_t *__restrict__ amap, const float *__restrict__ hw0,
+                                         const float *__restrict__ hw1, int na, float *__restrict__ hpart) {
+    constexpr int K = 576, NK = 18, KC = K / 64;
+    constexpr int NT = 64 * WGM * WGN;
+    constexpr int WTM = BM / WGM, WTN = BN / WGN;
+    constexpr int TM = WTM / 32, TN = WTN / 32;
+    constexpr int NR = 2 * (TM + TN), NM = 3 * TM * TN;
+    static_assert(NM >= NR, "a read behind every MFMA");
+    static_assert((BM * 8) % NT == 0 && (BN * 8) % NT == 0, "whole DMA instructions per thread");
+    constexpr int GA = BM * 8 / NT, GB = BN * 8 / NT, G = GA + GB;
+    constexpr int GX = (BM * KC + NT - 1) / NT, XS = GX * NT;  // row map DMAs per thread; ints per buffer
+    constexpr int STG = (BM + BN) * 8;
+    constexpr uint32_t STG_B = STG * 16;
+    constexpr int S = TM * TN * 16 + (EPI == 2 ? 2 * TM : 0);  // stores per wave and tile
+    constexpr int CARRY = S + G < 63 ? S + G : 63;
+    const int N_ = N;
+    static_assert(EPI == 1 || EPI == 2, "bias + ReLU, heads optional");
+    static_assert(EPI != 2 || (TN == 2 && WTN == 64), "heads epilogue: a wave tile 64 columns wide");
+    __shared__ p_u32x4 lds[3 * STG];
+    __shared__ int32_t gmap[2 * XS];
+
+    int v = blockIdx.x;
+    const int nb = gridDim.x;
+    if (v >= W) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int wm = w / WGN, wn = w - (w / WGN) * WGN;
+    const int fr = lane & 31, fh = lane >> 5;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) p_u32x4 *)lds;
+    const uint32_t gm0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int32_t *)gmap;
+    const uint32_t wbase = (uint32_t)__builtin_amdgcn_readfirstlane(w) * 64u;
+
+    PItem cur = p_item(v, W, tiles, tiles_n, BM, BN);
+    int lt = -1, ln = -1, eA = 0, eB = 0;
+    float bvv[TN], wv[4][TN];
+    auto load_consts = [&]() __attribute__((always_inline)) {  // (k_h3_pqg's epilogue loads)
+        lt = cur.t, ln = cur.n0;
+        eA = p_exp(p_amax(amaxA + lt)), eB = p_exp(p_amax(amaxB + lt));
+        const float *hw = lt == 0 ? hw0 : hw1;
+        const int nh = lt == 0 ? na : 1;
+#pragma unroll
+        for (int j = 0; j < TN; j++) {
+            const int col = ln + wn * WTN + j * 32 + fr;
+            bvv[j] = bias[(int64_t)lt * N + col];
+#pragma unroll
+            for (int o = 0; o < 4; o++) {
+                if constexpr (EPI == 2) {
+                    const float x = hw[(int64_t)(o < nh ? o : 0) * N + col];
+                    wv[o][j] = o < nh ? x : 0.0f;
+                } else {
+                    wv[o][j] = 0.0f;
+                }
+            }
+        }
+        p_drain_loads();
+    };
+    load_consts();
+
+    int ga[GA];
+    uint32_t ca[GA], offB[GB];
+#pragma unroll
+    for (int i = 0; i < GA; i++) {
+        const int q = i * NT + tid, r = q >> 3;
+        ga[i] = r * KC;
+        ca[i] = (uint32_t)((q & 7) ^ p_swz(r)) * 16u;
+    }
+#pragma unroll
+    for (int i = 0; i < GB; i++) {
+        const int q = i * NT + tid, r = q >> 3;
+        offB[i] = (uint32_t)(r * (K / 4) + ((q & 7) ^ p_swz(r))) * 16u;
+    }
+    // (every DMA source is a uniform base + a 32-bit byte offset per lane: the launcher refuses operands past 4 GB)
+    // the row map of the tile at m0 into buffer bf (rows past M - 1 clamped: read, never stored; the entries past
+    // the tile's BM x KC repeat its last)
+    auto issue_map = [&](int64_t m0, int bf) __attribute__((always_inline)) {
+        int tl = tid;  // opaque per tile: the entries' rows and chunks are made here, not kept across the walk
+        asm volatile("" : "+v"(tl));
+        const int mr = (int)(M - 1 - m0);  // (M x KC fits 32 bits: the launcher's test)
+#pragma unroll
+        for (int i = 0; i < GX; i++) {
+            const int e = std::min(i * NT + tl, BM * KC - 1), r = e / KC;
+            p_dma4s(amap + m0 * KC, (uint32_t)(std::min(r, mr) * KC + (e - r * KC)) * 4u,
+                    gm0 + (uint32_t)(bf * XS + i * NT) * 4u + wbase * 4u);
+        }
+    };
+    // the byte offsets of step kt's A sources (its chunk rows are 256 B each)
+    auto read_g = [&](int kt, uint32_t (&g)[GA], int bf) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < GA; i++)
+            g[i] = (uint32_t)*(const lds_i32 *)(uintptr_t)(gm0 + (uint32_t)(bf * XS + ga[i] + kt / 2) * 4u) * 256u +
+                   ca[i];
+    };
+    const p_u32x4 *At, *baseB;  // of the item the DMAs are issued for
+    auto set_base = [&](const PItem &it) __attribute__((always_inline)) {
+        At = A + it.t * sA;
+        baseB = B + it.t * sB + (int64_t)it.n0 * (K / 4);
+    };
+    auto issue = [&](auto KT, int st, const uint32_t (&g)[GA]) __attribute__((always_inline)) {
+        constexpr int kt = decltype(KT)::value;
+        const uint32_t base = lds0 + (uint32_t)(st * STG) * 16u + wbase * 16u;
+#pragma unroll
+        for (int i = 0; i < GA; i++) p_dma16s(At + 8 * (kt & 1), g[i], base + (uint32_t)(i * NT) * 16u);
+#pragma unroll
+        for (int i = 0; i < GB; i++) p_dma16s(baseB + kt * 8, offB[i], base + (uint32_t)((GA + i) * NT) * 16u);
+    };
+
+    uint32_t adA[2][2], adB[2][2];
+    {
+        const int ra = wm * WTM + fr, rb = BM + wn * WTN + fr;
+#pragma unroll
+        for (int kh = 0; kh < 2; kh++)
+#pragma unroll
+            for (int p = 0; p < 2; p++) {
+                const int c = 2 * (2 * kh + fh) + p;
+                adA[kh][p] = lds0 + (uint32_t)(ra * 8 + (c ^ p_swz(ra))) * 16u;
+                adB[kh][p] = lds0 + (uint32_t)(rb * 8 + (c ^ p_swz(rb))) * 16u;
+            }
+    }
+    struct Frag {
+        p_u32x4 a[TM][2], b[TN][2];
+    };
+    p_f32x16 hi[TM][TN], lo[TM][TN];
+    auto zero = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < TM; i++)
+#pragma unroll
+            for (int j = 0; j < TN; j++) {
+                hi[i][j] = p_f32x16{};
+                lo[i][j] = p_f32x16{};
+            }
+    };
+    zero();
+    auto rd = [&](Frag &g, auto K_, uint32_t so, auto KH) __attribute__((always_inline)) {
+        constexpr int k = decltype(K_)::value, kh = decltype(KH)::value;
+        if constexpr (k < 2 * TM)
+            lds_rd(g.a[k >> 1][k & 1], adA[kh][k & 1] + so + (k >> 1) * 32 * 128);
+        else
+            lds_rd(g.b[(k - 2 * TM) >> 1][k & 1], adB[kh][k & 1] + so + ((k - 2 * TM) >> 1) * 32 * 128);
+    };
+    auto mf = [&](const Frag &f, auto M_) __attribute__((always_inline)) {
+        constexpr int m = decltype(M_)::value, i = m / (3 * TN), j = (m / 3) % TN, pr = m % 3;
+        if constexpr (pr == 0)
+            lo[i][j] = p_mfma(f.a[i][1], f.b[j][0], lo[i][j]);
+        else if constexpr (pr == 1)
+            lo[i][j] = p_mfma(f.a[i][0], f.b[j][1], lo[i][j]);
+        else
+            hi[i][j] = p_mfma(f.a[i][0], f.b[j][0], hi[i][j]);
+    };
+    auto half = [&](const Frag &f, Frag &g, uint32_t so, auto KH, auto READS) __attribute__((always_inline)) {
+        static_for<NM>([&](auto M_) __attribute__((always_inline)) {
+            mf(f, M_);
+            if constexpr (decltype(READS)::value && decltype(M_)::value < NR) rd(g, M_, so, KH);
+        });
+        if constexpr (decltype(READS)::value) {
+            static_for<NR>([&](auto) __attribute__((always_inline)) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            });
+            if constexpr (NM > NR) __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto touch = [&](const Frag &f) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < TM; i++) asm volatile("" ::"v"(f.a[i][0]), "v"(f.a[i][1]));
+#pragma unroll
+        for (int j = 0; j < TN; j++) asm volatile("" ::"v"(f.b[j][0]), "v"(f.b[j][1]));
+    };
+    auto publish = [&]() __attribute__((always_inline)) {
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // k_h3_pqg's epilogues on the item cur
+    auto store_tile = [&](auto FULL) __attribute__((always_inline)) {
+        constexpr bool full = decltype(FULL)::value;
+        const float inv = p_pow2(-eA), invB = p_pow2(-eB);
+        float *Ct = C + cur.t * sC;
+        const int64_t m0 = cur.m0;
+        const int n0 = cur.n0;
+        // opaque per tile: the store addresses are made here, not hoisted out of the walk and kept (or spilled)
+        int64_t N = N_;
+        int rw = wm * WTM + 4 * fh, rp = wm * WTM + 4 * fh;
+        asm volatile("" : "+s"(N), "+v"(rw), "+v"(rp));
+        if constexpr (EPI == 2) {
+            float *part = hpart + ((int64_t)(cur.t * tiles_n + cur.tn) * WGN + wn) * M * 4;
+#pragma unroll
+            for (int i = 0; i < TM; i++) {
+                float pv[64];
+#pragma unroll
+                for (int q = 0; q < 64; q++) pv[q] = 0.0f;
+#pragma unroll
+                for (int j = 0; j < TN; j++) {
+                    const int col = n0 + wn * WTN + j * 32 + fr;
+#pragma unroll
+                    for (int r = 0; r < 16; r++) {
+                        const int64_t row = m0 + rw + i * 32 + (r & 3) + 8 * (r >> 2);
+                        const float x = p_relu((hi[i][j][r] + lo[i][j][r] * P_LO_INV) * inv * invB + bvv[j]);
+                        if (full || row < M) Ct[row * N + col] = x;
+#pragma unroll
+                        for (int o = 0; o < 4; o++) pv[o * 16 + r] += x * wv[o][j];
+                    }
+                }
+#pragma unroll
+                for (int c = 64, off = 16; off >= 1; c >>= 1, off >>= 1) {
+                    const bool up = (fr & off) != 0;
+#pragma unroll
+                    for (int k = 0; k < c / 2; k++) {
+                        const float send = up ? pv[k] : pv[k + c / 2], keep = up ? pv[k + c / 2] : pv[k];
+                        pv[k] = keep + __shfl_xor(send, off);
+                    }
+                }
+                const int o = fr >> 3;
+#pragma unroll
+                for (int k = 0; k < 2; k++) {
+                    const int r = 2 * (fr & 7) + k;
+                    const int64_t row = m0 + rp + i * 32 + (r & 3) + 8 * (r >> 2);
+                    if (full || row < M) part[row * 4 + o] = pv[k];
+                }
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < TN; j++) {
+                const int col = n0 + wn * WTN + j * 32 + fr;
+#pragma unroll
+                for (int i = 0; i < TM; i++) {
+#pragma unroll
+                    for (int r = 0; r < 16; r++) {
+                        const int64_t row = m0 + rw + i * 32 + (r & 3) + 8 * (r >> 2);
+                        if (full || row < M)
+                            Ct[row * N + col] = p_relu((hi[i][j][r] + lo[i][j][r] * P_LO_INV) * inv * invB + bvv[j]);
+                    }
+                }
+            }
+        }
+    };
+
+    int cb = 0;  // the row map buffer of the item cur
+    issue_map(cur.m0, cb);
+    P_VMCNT(0);
+    publish();
+    set_base(cur);
+    uint32_t g0[GA], g1[GA];  // A sources of the next issue (ping-pong, compile-time choice: NK is even)
+    read_g(0, g0, cb);
+    issue(IC<0>{}, 0, g0);
+    read_g(1, g1, cb);
+    issue(IC<1>{}, 1, g1);
+    read_g(2, g0, cb);
+    P_VMCNT(G);
+    publish();
+    bool carried = false;
+    for (;;) {
+        const bool more = v + nb < W;
+        const PItem nxt = more ? p_item(v + nb, W, tiles, tiles_n, BM, BN) : cur;
+        Frag f0, f1;
+        static_for<NR>([&](auto K_) __attribute__((always_inline)) { rd(f0, K_, 0, IC<0>{}); });
+        static_for<NK>([&](auto KT) __attribute__((always_inline)) {
+            constexpr int kt = decltype(KT)::value, st = kt % 3, sn = (kt + 1) % 3;
+            uint32_t(&gu)[GA] = (kt % 2 == 0) ? g0 : g1;  // holds step kt + 2's sources
+            uint32_t(&gn)[GA] = (kt % 2 == 0) ? g1 : g0;
+            if constexpr (kt == NK - 2) set_base(nxt);  // from here on the DMAs are the next item's
+            issue(IC<(kt + 2) % NK>{}, (kt + 2) % 3, gu);
+            if constexpr (kt == 8) issue_map(nxt.m0, cb ^ 1);
+            __builtin_amdgcn_sched_barrier(0);
+            half(f0, f1, (uint32_t)st * STG_B, IC<1>{}, IC<1>{});
+            touch(f1);
+            // step kt + 1 landed; what was issued behind it may stay in flight: the step just issued, at steps 8
+            // and 9 the row map's DMAs too, and behind a tile's first step the stores of the tile before it
+            if constexpr (kt == 0) {
+                if (carried)
+                    P_VMCNT(CARRY);
+                else
+                    P_VMCNT(G);
+            } else if constexpr (kt == 8 || kt == 9) {
+                P_VMCNT(G + GX);
+            } else {
+                P_VMCNT(G);
+            }
+            publish();
+            read_g((kt + 3) % NK, gn, kt + 3 < NK ? cb : cb ^ 1);
+            if constexpr (kt + 1 < NK)
+                half(f1, f0, (uint32_t)sn * STG_B, IC<0>{}, IC<1>{});
+            else
+                half(f1, f0, 0u, IC<0>{}, IC<0>{});
+        });
+        if (cur.t != lt || cur.n0 != ln) load_consts();
+        carried = cur.m0 + BM <= M;
+        if (carried) {
+            store_tile(IC<1>{});
+        } else {
+            store_tile(IC<0>{});
+            P_VMCNT(0);
+        }
+        zero();
+        if (!more) break;
+        v += nb;
+        cur = nxt;
+        cb ^= 1;
+    }
+    P_VMCNT(0);  // the last tile's look-ahead DMAs: landed before the block's LDS is given away
+}
+
+// PERS (appended behind the one-tile forms' parameters, so their names stay prefixes): the walk above.  tiles: row
+// x column tiles of one tower; the one-tile form's grid is (tiles, T), the walk's at most one block per CU
+template <int BM, int BN, int WGM, int WGN, int EPI, int NK, int NS = 3, bool ONE = false, int ORD = 0,
+          bool PERS = false>
+__global__ __launch_bounds__(64 * WGM * WGN) void k_h3_pq(const p_u32x4 *__restrict__ A, const p_u32x4 *__restrict__ B,
+                                                          const uint32_t *__restrict__ amaxA,
+                                                          const uint32_t *__restrict__ amaxB, int64_t M, int N, int K,
+                                                          int64_t sA, int64_t sB, const float *__restrict__ bias,
+                                                          float *__restrict__ C, int64_t sC, int tiles_n, int tiles,
+                                                          int W) {
+    if constexpr (PERS) {
+        static_assert(NS == 3 && !ONE, "the walk: a 3-stage ring, two accumulators");
+        pq_walk<BM, BN, WGM, WGN, EPI, NK, ORD>(A, B, amaxA, amaxB, M, N, K, sA, sB, bias, C, sC, tiles_n, tiles, W);
+    } else {
+        pq_tile<BM, BN, WGM, WGN, EPI, NK, NS, ONE, ORD>(A, B, amaxA, amaxB, M, N, K, sA, sB, bias, C, sC, tiles_n);
+    }
+}
+
+template <int BM, int BN, int WGM, int WGN, int EPI, bool PERS = false>
+__global__ __launch_bounds__(64 * WGM * WGN) void k_h3_pqg(const p_u32x4 *__restrict__ A, const p_u32x4 *__restrict__ B,
+                                                           const uint32_t *__restrict__ amaxA,
+                                                           const uint32_t *__restrict__ amaxB, int64_t M, int N,
+                                                           int64_t sA, int64_t sB, const float *__restrict__ bias,
+                                                           float *__restrict__ C, int64_t sC, int tiles_n, int tiles,
+                                                           int W, const int32_t *__restrict__ amap,
+                                                           const float *__restrict__ hw0, const float *__restrict__ hw1,
+                                                           int na, float *__restrict__ hpart) {
+    if constexpr (PERS)
+        pqg_walk<BM, BN, WGM, WGN, EPI>(A, B, amaxA, amaxB, M, N, sA, sB, bias, C, sC, tiles_n, tiles, W, amap, hw0,
+                                        hw1, na, hpart);
+    else
+        pqg_tile<BM, BN, WGM, WGN, EPI>(A, B, amaxA, amaxB, M, N, sA, sB, bias, C, sC, tiles_n, amap, hw0, hw1, na,
+                                        hpart);
+}
+
+// blocks of a walk: one per CU of the current device, or the override (tests: walks that do not depend on the CU
+// count), never more than there are items
+int g_walk_blocks = 0;  // set_h3p_walk_blocks
+int walk_blocks(int64_t items) {
+    int n = g_walk_blocks;
+    if (n <= 0) {
+        static int cus[64];  // per device, 0 = not asked yet
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
+        if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+            return -1;
+        n = cus[dev];
+    }
+    return n <= 0 ? -1 : (int)std::min<int64_t>(n, items);
+}
+
+template <int BM, int BN, int WGM, int WGN, int NS = 3, bool ONE = false, int ORD = 0, bool PERS = false>
+hipError_t pq_launch(const void *A, const void *B, const uint32_t *amaxA, const uint32_t *amaxB, int64_t M, int N,
+                     int K, int T, int64_t sA, int64_t sB, const float *bias, float *C, int64_t sC, hipStream_t s) {
+    if (N % BN || K % 32 || K < 64) return hipErrorInvalidValue;
+    const int64_t tiles_m = (M + BM - 1) / BM;
+    const int tiles_n = N / BN;
+    if (tiles_m * tiles_n * T > INT32_MAX) return hipErrorInvalidValue;
+    const int tiles = (int)(tiles_m * tiles_n), W = tiles * T;
+    dim3 grid((unsigned)tiles, T);
+    const dim3 block(64 * WGM * WGN);
+    if constexpr (PERS) {
+        const int nb = walk_blocks(W);
+        if (nb < 1) return hipErrorInvalidValue;
+        grid = dim3(nb);
+    }
+    const auto *a = static_cast<const p_u32x4 *>(A);
+    const auto *b = static_cast<const p_u32x4 *>(B);
+#define PQ_K(NK)                                                                                                    \
+    do {                                                                                                            \
+        if (bias)                                                                                                   \
+            hipLaunchKernelGGL((k_h3_pq<BM, BN, WGM, WGN, 1, NK, NS, ONE, ORD, PERS>), grid, block, 0, s, a, b, amaxA, \
+                               amaxB, M, N, K, sA / 4, sB / 4, bias, C, sC, tiles_n, tiles, W);                     \
+        else                                                                                                        \
+            hipLaunchKernelGGL((k_h3_pq<BM, BN, WGM, WGN, 0, NK, NS, ONE, ORD, PERS>), grid, block, 0, s, a, b, amaxA, \
+                               amaxB, M, N, K, sA / 4, sB / 4, nullptr, C, sC, tiles_n, tiles, W);                  \
+    } while (0)
+    switch (K) {  // the k loop is unrolled: one instantiation per depth (fc1's forward K = 576, input gradient 512)
+        case 576: PQ_K(18); break;
+        case 512: PQ_K(16); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef PQ_K
+    return hipGetLastError();
+}
+
+
 }  // namespace
 
+// the walks' block count: 0 = one block per CU (the default), n > 0 = n blocks (tests of the tile walk)
+void set_h3p_walk_blocks(int n) { g_walk_blocks = n > 0 ? n : 0; }
+
 // A, B: plane images (4 B per value, strides in values); cfg 60: 128 x 256 tiles (2 x 4 waves),
-// 62: 128 x 192 (4 x 2 waves of 32 x 96: N = 576)
+// 62: 128 x 192 (4 x 2 waves of 32 x 96: N = 576).  The gathered forward's and cfg 62's kernels each have a one-tile
+// form (a block per tile: 75 forward, 77 input gradient) and a persistent one (a block per CU walking tiles: 76, 78;
+// the same bits); 60 and 62, the update's, are whichever of the two H3P_FWD_WALK / H3P_DGRAD_WALK names
+constexpr bool H3P_FWD_WALK = true, H3P_DGRAD_WALK = true;
 hipError_t launch_h3p_gemm_nt(const void *A, const uint32_t *amaxA, const void *B, const uint32_t *amaxB, int64_t M,
                               int N, int K, int T, int64_t a_stride, int64_t b_stride, const float *bias, float *C,
                               int64_t c_stride, int cfg, hipStream_t s, const int32_t *a_rows, const float *head_w0,
@@ -796,25 +1441,42 @@ hipError_t launch_h3p_gemm_nt(const void *A, const uint32_t *amaxA, const void *
     if (a_stride % 4 || b_stride % 4) return hipErrorInvalidValue;
     if (a_rows) {  // the forward over a3's gathered planes (cfg 60 tiles, K = 576), bias + ReLU, heads optional
         constexpr int BM = 128, BN = 256;
-        if (cfg != 60 || K != 576 || N % BN || !bias || !C) return hipErrorInvalidValue;
+        if ((cfg != 60 && cfg != 75 && cfg != 76) || K != 576 || N % BN || !bias || !C) return hipErrorInvalidValue;
         if (head_part && (T != 2 || n_actions < 1 || n_actions > 4 || !head_w0 || !head_w1)) return hipErrorInvalidValue;
         const int64_t tiles_m = (M + BM - 1) / BM;
         const int tiles_n = N / BN;
-        const dim3 grid((unsigned)(tiles_m * tiles_n), T), block(512);
+        if (tiles_m * tiles_n * T > INT32_MAX) return hipErrorInvalidValue;
+        const int tiles = (int)(tiles_m * tiles_n), W = tiles * T;
+        const bool walk = cfg == 76 || (cfg == 60 && H3P_FWD_WALK);
+        // the walk's DMA sources are 32-bit byte offsets from uniform bases: a tower of A, B's tile rows, the row map
+        if (walk && (a_stride > (INT64_C(1) << 30) || M * 9 > (INT64_C(1) << 30))) return hipErrorInvalidValue;
+        const int nb = walk ? walk_blocks(W) : 0;
+        if (walk && nb < 1) return hipErrorInvalidValue;
+        const dim3 grid = walk ? dim3(nb) : dim3((unsigned)tiles, T), block(512);
         const auto *a = static_cast<const p_u32x4 *>(A);
         const auto *b = static_cast<const p_u32x4 *>(B);
-        if (head_part)
-            hipLaunchKernelGGL((k_h3_pqg<BM, BN, 2, 4, 2>), grid, block, 0, s, a, b, amaxA, amaxB, M, N, a_stride / 4,
-                               b_stride / 4, bias, C, c_stride, tiles_n, a_rows, head_w0, head_w1, n_actions,
-                               head_part);
+#define PQG(EPI, PERS, ...)                                                                                          \
+    hipLaunchKernelGGL((k_h3_pqg<BM, BN, 2, 4, EPI, PERS>), grid, block, 0, s, a, b, amaxA, amaxB, M, N, a_stride / 4, \
+                       b_stride / 4, bias, C, c_stride, tiles_n, tiles, W, a_rows, __VA_ARGS__)
+        if (head_part && walk)
+            PQG(2, true, head_w0, head_w1, n_actions, head_part);
+        else if (head_part)
+            PQG(2, false, head_w0, head_w1, n_actions, head_part);
+        else if (walk)
+            PQG(1, true, nullptr, nullptr, 0, nullptr);
         else
-            hipLaunchKernelGGL((k_h3_pqg<BM, BN, 2, 4, 1>), grid, block, 0, s, a, b, amaxA, amaxB, M, N, a_stride / 4,
-                               b_stride / 4, bias, C, c_stride, tiles_n, a_rows, nullptr, nullptr, 0, nullptr);
+            PQG(1, false, nullptr, nullptr, 0, nullptr);
+#undef PQG
         return hipGetLastError();
     }
     switch (cfg) {
         case 60: return pq_launch<128, 256, 2, 4>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
-        case 62: return pq_launch<128, 192, 4, 2>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
+        case 62:
+            if (H3P_DGRAD_WALK)
+                return pq_launch<128, 192, 4, 2, 3, false, 0, true>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
+            return pq_launch<128, 192, 4, 2>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
+        case 77: return pq_launch<128, 192, 4, 2>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
+        case 78: return pq_launch<128, 192, 4, 2, 3, false, 0, true>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
         // round 6: the same with a 4-stage ring (160 KB of LDS, three k steps in flight)
         case 63: return pq_launch<128, 192, 4, 2, 4>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
         // round 6: one accumulator per tile (ONE): 65: 256 x 192 tiles on a 2-stage ring (112 KB), 66: 62's 128 x 192

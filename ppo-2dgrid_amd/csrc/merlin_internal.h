@@ -300,6 +300,8 @@ hipError_t launch_h3p_gemm_nt(const void *A, const uint32_t *amaxA, const void *
                               int64_t c_stride, int cfg, hipStream_t s, const int32_t *a_rows = nullptr,
                               const float *head_w0 = nullptr, int n_actions = 0, const float *head_w1 = nullptr,
                               float *head_part = nullptr);
+// blocks of the persistent NT kernels' tile walk (launch_h3p_gemm_nt cfg 76 / 78): 0 = one per CU, n > 0 = n
+void set_h3p_walk_blocks(int n);
 hipError_t launch_h3p_gemm_tn_gather(const void *A, const uint32_t *amaxA, const void *B, const uint32_t *amaxB,
                                      int64_t Kd, int M, int N, int T, int64_t a_stride, int64_t b_stride, int splits,
                                      float *slab, const int32_t *b_rows, int cfg, int *S_out, hipStream_t s);

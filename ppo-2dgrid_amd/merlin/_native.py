@@ -246,6 +246,7 @@ EXPORTED_SYMBOLS = (
     "merlin_env_set_difficulties", "merlin_episode_class_stats",
     "merlin_frame_atlas", "merlin_render_frames", "merlin_env_render", "merlin_env_snapshot",
     "merlin_shortest_paths", "merlin_env_optimal_steps", "merlin_shortest_paths_host",
+    "merlin_h3_walk_blocks",
 )
 
 
@@ -1307,6 +1308,8 @@ def x6_gemm_tn(A: torch.Tensor, B: torch.Tensor, splits: int | None = None, cfg:
 # 128 x 256 and input gradient 128 x 192 tiles (scripts/ab_update.py, same update replayed: 204.5 vs 209.0 ms for cfg 0 / 1)
 # rollout: 4,096 rows; qall: [5^9, 64] x [64, 576] (k_h3_nt, not the input gradient's k_h3_ntp instantiation, so
 # profiles keep the two apart); qwin / qwin_dgrad: the update's window GEMMs (N = 576, K = 64 / N = 64, K = 576)
+# dgrad_planes 62 / fwd_planes 60: the persistent LDS-DMA kernels (merlin_h3p.hip; 77 / 75 select their one-tile forms,
+# 78 / 76 the persistent ones whatever 62 / 60 mean)
 H3_NT_CFG = {"fwd": 13, "dgrad": 11, "rollout": 12, "qall": 1, "qwin": 11, "qwin_dgrad": 5, "dgrad_planes": 62, "fwd_planes": 60}
 H3_TN_CFG = 0
 H3_TN_CFG_PLANES = 20  # the weight gradient over both operands' planes: the LDS-DMA TN (merlin_h3p.hip k_h3_tq)
@@ -1414,11 +1417,27 @@ def h3_gemm_nt(A: torch.Tensor, amaxA: torch.Tensor, B: torch.Tensor, amaxB: tor
     return out
 
 
+@contextlib.contextmanager
+def h3_walk_blocks(blocks: int):
+    """Within the block, the persistent plane-operand NT kernels (h3_gemm_nt_planes cfg 62 / 78, h3_gemm_nt_heads over
+    planes cfg 60 / 76) launch `blocks` blocks instead of one per CU (merlin_h3_walk_blocks; never more than there are
+    tiles): tests of the tile walk that must not depend on the device's CU count.  Process-wide, not for captures."""
+    fn = lib().merlin_h3_walk_blocks
+    fn.argtypes, fn.restype = [C.c_int32], C.c_int
+    check(fn(int(blocks)), "merlin_h3_walk_blocks")
+    try:
+        yield
+    finally:
+        check(fn(0), "merlin_h3_walk_blocks")
+
+
 def h3_gemm_nt_planes(Ap: torch.Tensor, amaxA: torch.Tensor, B: torch.Tensor, amaxB: torch.Tensor,
                       bias: torch.Tensor | None = None, cfg: int = 62, out: torch.Tensor | None = None,
                       name: str = "h3_gemm_nt") -> torch.Tensor:
     """h3_gemm_nt with A already in plane form, Ap int16[T, M, 2K] scaled by amaxA's exponent (e.g. head_bwd's dz
-    planes): merlin_h3_gemm_nt_planes, both operands by LDS-DMA (cfg 60 / 62 and the alternates 63 / 65 / 66 / 68 / 69, K = 512 or 576)."""
+    planes): merlin_h3_gemm_nt_planes, both operands by LDS-DMA (cfg 60 / 62 and the alternates 63 / 65 / 66 / 68 / 69, K = 512 or 576; 62 is the
+    persistent kernel, one block per CU walking tiles, also selectable as 78; 77 is the same tile with a block per
+    tile: the same bits)."""
     H3_SPANS.add(name)
     T, M, K2 = (int(v) for v in Ap.shape)
     K = K2 // 2
@@ -1439,18 +1458,19 @@ def h3_gemm_nt_planes(Ap: torch.Tensor, amaxA: torch.Tensor, B: torch.Tensor, am
 
 def h3_gemm_nt_heads(A: torch.Tensor, amaxA: torch.Tensor, B: torch.Tensor, amaxB: torch.Tensor, bias: torch.Tensor,
                      Wa: torch.Tensor, Wc: torch.Tensor, cfg: int, rows: torch.Tensor | None = None,
-                     name: str = "h3_gemm_nt", partials_only: bool = False) -> tuple:
+                     name: str = "h3_gemm_nt", partials_only: bool = False, heads: bool = True) -> tuple:
     """(h, logits, value): h = relu(A @ B^T + bias) per tower as h3_gemm_nt (A f32[2, M, K], B planes), with the heads
     logits [M, A] = h[0] Wa^T and value [M] = h[1] wc (no biases) from partial dot products made in the GEMM's
     epilogue (merlin_h3_gemm_nt_heads) and summed in order (merlin_heads_combine, span "k_heads_fwd").
     partials_only: h is not written and the heads' partials float[2, parts, M, 4] are returned as they are (for
-    act_draw)."""
+    act_draw).  heads=False (A as planes only): the bias + ReLU epilogue alone, h is returned."""
     H3_SPANS.add(name)
     T, M, K = (int(v) for v in A.shape)
     ap = A.dtype == torch.int16  # A as planes (window_conv3_planes): merlin_h3_gemm_nt_heads_planes, gathered only
     if ap:
         K //= 2
         assert rows is not None and not partials_only
+    assert heads or ap
     N = int(B.shape[1])
     NA = int(Wa.shape[0])
     assert T == 2 and A.dtype in (torch.float32, torch.int16) and B.dtype == torch.int16 and B.shape == (T, N, 2 * K)
@@ -1461,13 +1481,15 @@ def h3_gemm_nt_heads(A: torch.Tensor, amaxA: torch.Tensor, B: torch.Tensor, amax
     if rows is not None:
         assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.numel() == M * K // 64
     out = None if partials_only else torch.empty((T, M, N), dtype=torch.float32, device=A.device)
-    part = torch.empty((T, P, M, 4), dtype=torch.float32, device=A.device)
+    part = torch.empty((T, P, M, 4), dtype=torch.float32, device=A.device) if heads else None
     fn = lib().merlin_h3_gemm_nt_heads_planes if ap else lib().merlin_h3_gemm_nt_heads
     with KernelTimer.span(name, 0, 2 * T * M * N * K):
         check(fn(ptr(A), ptr(amaxA), ptr(B), ptr(amaxB), M, N, K, M * K, N * K, ptr(bias), ptr(out), M * N, ptr(rows),
                  ptr(Wa), NA, ptr(Wc), ptr(part), int(cfg), stream_of(A)), "merlin_h3_gemm_nt_heads")
     if partials_only:
         return part
+    if not heads:
+        return out
     logits = torch.empty((M, NA), dtype=torch.float32, device=A.device)
     value = torch.empty(M, dtype=torch.float32, device=A.device)
     with KernelTimer.span("k_heads_fwd", T * P * M * 16 + M * (NA + 1) * 4):

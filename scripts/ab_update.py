@@ -77,7 +77,10 @@ def main():
             FS.PREFILL = "noprefill" not in name  # conv3's backward fills beside the weight gradient
             FS.WINDOW_BWD_HIP = "nowinbwd" not in name  # the window GEMM's backward on hipBLASLt + torch
             nat.H3_TN_CFG_PLANES = 0 if "tngplanes" in name else 21 if "tq21" in name else 20  # register-staged / 64-row
-            nat.H3_NT_CFG["fwd_planes"] = 13 if "ntpgplanes" in name else 60  # the copy-staged forward over planes
+            # the forward over planes: copy-staged (13), or the LDS-DMA kernel's cfg (h3qNN: 75 one tile per block,
+            # 76 persistent; h3pNN likewise for the input gradient: 77 / 78)
+            nat.H3_NT_CFG["fwd_planes"] = 13 if "ntpgplanes" in name else next(
+                (int(t[3:]) for t in name.split("_") if t[:3] == "h3q"), 60)
             nat.H3_NT_CFG["dgrad_planes"] = next((int(t[3:]) for t in name.split("_") if t[:3] == "h3p"), 62)
             nat.X6_NT_CFG["fwd"] = 28 if "fwd28" in name else 20
             nat.X6_NT_CFG["dgrad"] = 27 if "dgrad27" in name else 22
