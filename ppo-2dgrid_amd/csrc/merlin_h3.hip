@@ -37,27 +37,15 @@ typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 typedef __attribute__((address_space(3))) char lds_char;
 
 constexpr int BK = 32;           // k per step
-constexpr float LO_INV = 1.0f / 2048.0f;
+constexpr float LO_INV = H3_LO_INV;
 
 __device__ __forceinline__ f32x16 mfma16(const u32x4 a, const u32x4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0,
                                                    0);
 }
 
-__device__ __forceinline__ float relu_nan(float v) { return v != v ? v : fmaxf(v, 0.0f); }
-
-__device__ __forceinline__ int xcd_tile(int b, int nb) {
-    const int xcd = b & 7, q = nb >> 3, r = nb & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-}
-
-// h3_exp / pow2f / h3_pair: merlin_internal.h (shared with the producers that write planes)
-
-// an operand scale written by another kernel's atomics: read with a vector load at agent scope (L2-coherent), not
-// through the scalar data cache a wave-uniform load would take
-__device__ __forceinline__ uint32_t load_amax(const uint32_t *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// relu_nan / xcd_tile / h3_exp / pow2f / load_amax / h3_pair: merlin_internal.h (shared with merlin_h3p.hip and the
+// producers that write planes)
 
 // 8 consecutive values (two float4) scaled by sc (sc2 = 2^11 sc) -> hi chunk p0, lo chunk p1
 __device__ __forceinline__ void h3_split8(const float4 a, const float4 b, float sc, float sc2, u32x4 &p0, u32x4 &p1) {

@@ -27,31 +27,15 @@ typedef _Float16 p_f16x8 __attribute__((ext_vector_type(8)));
 typedef float p_f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t p_u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr float P_LO_INV = 1.0f / 2048.0f;
-
 __device__ __forceinline__ p_f32x16 p_mfma(const p_u32x4 a, const p_u32x4 b, p_f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(p_f16x8, a), __builtin_bit_cast(p_f16x8, b), c, 0,
                                                    0, 0);
-}
-__device__ __forceinline__ float p_relu(float v) { return v != v ? v : fmaxf(v, 0.0f); }
-__device__ __forceinline__ int p_xcd_tile(int b, int nb) {
-    const int xcd = b & 7, q = nb >> 3, r = nb & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-}
-__device__ __forceinline__ int p_exp(uint32_t amax) {  // merlin_h3.hip h3_exp
-    if (amax == 0u) return 0;
-    const int e = (int)((amax >> 23) & 0xffu) - 127;
-    return std::min(std::max(14 - e, -120), 115);
-}
-__device__ __forceinline__ float p_pow2(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
-__device__ __forceinline__ uint32_t p_amax(const uint32_t *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ int p_swz(int r) { return (r >> 1) & 7; }
 // a lo plane fragment (8 f16 at 2^11 x their value) back at scale: v_pk_mul_f16 x 4, exact unless the result is
 // subnormal (then rounded to the f16 subnormal grid, 2^-24)
 __device__ __forceinline__ p_u32x4 p_unscale(const p_u32x4 x) {
-    return __builtin_bit_cast(p_u32x4, __builtin_bit_cast(p_f16x8, x) * (_Float16)(1.0f / 2048.0f));
+    return __builtin_bit_cast(p_u32x4, __builtin_bit_cast(p_f16x8, x) * (_Float16)H3_LO_INV);
 }
 
 template <int V>
@@ -68,14 +52,205 @@ typedef __attribute__((address_space(3))) p_u32x4 lds_u32x4;
 // one 16-B LDS fragment read (a plain load: the k loop is unrolled, so the compiler's waits are exact counts)
 __device__ __forceinline__ void lds_rd(p_u32x4 &d, uint32_t addr) { d = *(const lds_u32x4 *)(uintptr_t)addr; }
 
-// NS: LDS stages of the DMA ring (NS - 1 k steps in flight).  3: 120 KB at 128 x 192; 4 (round 6): 160 KB, the whole
-// LDS of a CU -- a step's DMA is latency-bound (~2.5 us under load against ~1.2 us of MFMA work per step), so the
-// feed rate per CU is the bytes in flight over that latency
+// ---------------------------------------------------------------------------------------------------------------
+// What the four NT bodies below (pq_tile, pqg_tile, pq_walk, pqg_walk) share: a wave's accumulators, the fragment
+// reads and MFMAs of a half step over a staged k step, and the epilogues.  A body keeps what is its own: where its
+// DMAs read, its ring schedule and its waits.
 // ONE (round 6): one accumulator per tile -- the lo planes (stored 2^11 up) brought back to scale in registers
 // (v_pk_mul_f16 by 2^-11: exact while the result stays normal, f16 subnormals kept) so all three products of a k
 // step add into the same fp32 accumulator: half the accumulator registers, hence twice the tile area per byte staged.
 // Not the same bits as the two-accumulator kernels (a different summation); its error is held to float64 by
 // tests/test_gpu_h3.py like theirs.
+// ORD: the order of a half step's MFMAs, see mf.
+template <int BM, int BN, int WGM, int WGN, bool ONE = false, int ORD = 0>
+struct PCore {
+    static constexpr int NT = 64 * WGM * WGN;
+    static constexpr int WTM = BM / WGM, WTN = BN / WGN;
+    static constexpr int TM = WTM / 32, TN = WTN / 32;
+    static constexpr int NR = 2 * (TM + TN), NM = 3 * TM * TN;  // fragment reads / MFMAs per half step
+    static_assert(NM >= NR, "a read behind every MFMA");
+    static constexpr int GA = BM * 8 / NT, GB = BN * 8 / NT, G = GA + GB;  // DMA instructions per thread and k step
+    static_assert((BM * 8) % NT == 0 && (BN * 8) % NT == 0, "whole DMA instructions per thread");
+    static constexpr int STG = (BM + BN) * 8;  // chunks per stage
+    static constexpr uint32_t STG_B = STG * 16;
+    static constexpr int CS = TM * TN * 16;  // C stores per wave and tile
+
+    struct Frag {
+        p_u32x4 a[TM][2], b[TN][2];  // [tile][plane]
+    };
+    p_f32x16 hi[TM][TN], lo[TM][TN];
+    // fragment addresses (bytes, stage 0): A tile i / B tile j at half kh, plane p -> row r, chunk 2 (2 kh + fh) + p
+    uint32_t adA[2][2], adB[2][2];  // [kh][p], tile 0; tile i is +32 i rows (same swizzle)
+
+    __device__ __forceinline__ void init(uint32_t lds0, int wm, int wn, int fr, int fh) {
+        const int ra = wm * WTM + fr, rb = BM + wn * WTN + fr;
+#pragma unroll
+        for (int kh = 0; kh < 2; kh++)
+#pragma unroll
+            for (int p = 0; p < 2; p++) {
+                const int c = 2 * (2 * kh + fh) + p;
+                adA[kh][p] = lds0 + (uint32_t)(ra * 8 + (c ^ p_swz(ra))) * 16u;
+                adB[kh][p] = lds0 + (uint32_t)(rb * 8 + (c ^ p_swz(rb))) * 16u;
+            }
+        zero();
+    }
+    __device__ __forceinline__ void zero() {
+#pragma unroll
+        for (int i = 0; i < TM; i++)
+#pragma unroll
+            for (int j = 0; j < TN; j++) {
+                hi[i][j] = p_f32x16{};
+                lo[i][j] = p_f32x16{};
+            }
+    }
+    // the k-th of the NR fragment reads of half KH of the stage at byte offset so into g (k, KH compile-time: no
+    // runtime-indexed fragment arrays)
+    template <class K_, class KH>
+    __device__ __forceinline__ void rd(Frag &g, K_, uint32_t so, KH) const {
+        constexpr int k = K_::value, kh = KH::value;
+        if constexpr (k < 2 * TM)
+            lds_rd(g.a[k >> 1][k & 1], adA[kh][k & 1] + so + (k >> 1) * 32 * 128);
+        else
+            lds_rd(g.b[(k - 2 * TM) >> 1][k & 1], adB[kh][k & 1] + so + ((k - 2 * TM) >> 1) * 32 * 128);
+    }
+    // MFMA m: tile (i, j), product pr -- ORD 0: a tile's three products back to back (m / 3 = tile, m % 3 = pr);
+    // ORD 1: product-major (every tile's pr 0, then every tile's pr 1, ...), so consecutive MFMAs never share an
+    // accumulator; each accumulator still sums the same products in the same order (the same bits)
+    template <class M_>
+    __device__ __forceinline__ void mf(const Frag &f, const Frag &u, M_) {
+        constexpr int m = M_::value, tl = ORD ? m % (TM * TN) : m / 3, pr = ORD ? m / (TM * TN) : m % 3;
+        constexpr int i = tl / TN, j = tl % TN;
+        if constexpr (ONE) {  // u: f's lo planes at scale
+            if constexpr (pr == 0)
+                hi[i][j] = p_mfma(u.a[i][1], f.b[j][0], hi[i][j]);
+            else if constexpr (pr == 1)
+                hi[i][j] = p_mfma(f.a[i][0], u.b[j][1], hi[i][j]);
+            else
+                hi[i][j] = p_mfma(f.a[i][0], f.b[j][0], hi[i][j]);
+        } else if constexpr (pr == 0)
+            lo[i][j] = p_mfma(f.a[i][1], f.b[j][0], lo[i][j]);
+        else if constexpr (pr == 1)
+            lo[i][j] = p_mfma(f.a[i][0], f.b[j][1], lo[i][j]);
+        else
+            hi[i][j] = p_mfma(f.a[i][0], f.b[j][0], hi[i][j]);
+    }
+    // half step: the NM MFMAs on f, with the NR reads of g (stage offset so, half KH) one behind each of the first NR
+    // (sched_group_barrier: MFMA, read, MFMA, read, ...), so the reads of a half are waited for once, by the first
+    // MFMA that needs them, with the MFMAs still in the pipe covering the LDS round trip (the file's header)
+    template <class KH, class READS>
+    __device__ __forceinline__ void half(const Frag &f, Frag &g, uint32_t so, KH kh, READS) {
+        Frag u;
+        if constexpr (ONE) {
+#pragma unroll
+            for (int i = 0; i < TM; i++) u.a[i][1] = p_unscale(f.a[i][1]);
+#pragma unroll
+            for (int j = 0; j < TN; j++) u.b[j][1] = p_unscale(f.b[j][1]);
+        }
+        static_for<NM>([&](auto M_) __attribute__((always_inline)) {
+            mf(f, u, M_);
+            if constexpr (READS::value && decltype(M_)::value < NR) rd(g, M_, so, kh);
+        });
+        if constexpr (READS::value) {
+            static_for<NR>([&](auto) __attribute__((always_inline)) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            });
+            if constexpr (NM > NR) __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    // makes the compiler's wait for the reads of f fall here: before the barrier that follows, not behind it in front
+    // of the first MFMA of the next half
+    static __device__ __forceinline__ void touch(const Frag &f) {
+#pragma unroll
+        for (int i = 0; i < TM; i++) asm volatile("" ::"v"(f.a[i][0]), "v"(f.a[i][1]));
+#pragma unroll
+        for (int j = 0; j < TN; j++) asm volatile("" ::"v"(f.b[j][0]), "v"(f.b[j][1]));
+    }
+    // behind a body's own vmcnt wait: every wave's DMAs up to that count are in LDS, and no LDS read moves above
+    static __device__ __forceinline__ void publish() {
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+    }
+
+    __device__ __forceinline__ float acc(int i, int j, int r) const {
+        return ONE ? hi[i][j][r] : hi[i][j][r] + lo[i][j][r] * H3_LO_INV;
+    }
+    // The plain epilogue: C[row][col] = acc x inv x invB (EPI 1: + bias, ReLU) over the wave's part of the tile at
+    // row m0: rows m0 + rw + ..., rw = wm WTM + 4 fh; columns col0 + 32 j, col0 = n0 + wn WTN + fr; bv[j] their bias.
+    // FULL: every row of the tile exists, so the stores are unconditional (a walk counts them in its vmcnt waits)
+    template <class FULL, class EPI_>
+    __device__ __forceinline__ void store(FULL, EPI_, float *Ct, int64_t N, int64_t M, int64_t m0, int rw, int col0,
+                                          float inv, float invB, const float (&bv)[TN]) const {
+#pragma unroll
+        for (int j = 0; j < TN; j++) {
+            const int col = col0 + j * 32;
+#pragma unroll
+            for (int i = 0; i < TM; i++) {
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int64_t row = m0 + rw + i * 32 + (r & 3) + 8 * (r >> 2);
+                    if (FULL::value || row < M) {
+                        const float v = acc(i, j, r) * inv * invB;
+                        Ct[row * N + col] = EPI_::value == 1 ? relu_nan(v + bv[j]) : v;
+                    }
+                }
+            }
+        }
+    }
+    // The heads epilogue (merlin_h3.hip's h3_ntp_body EPI 2): bias + ReLU as above, and of the stored values the
+    // policy / value heads' partial dot products over the wave's 64 columns (wv[o][j]: head row o's weights of the
+    // lane's columns), two per lane into part[row][4] (rp: rw again, for the partials' rows): CS + 2 TM stores per
+    // wave.  Per i: the 16 rows x 4 head outputs of this lane's two columns, then a reduce-scatter over the 32 column
+    // lanes of the half-wave (xor 16 .. 1, each step keeping the half of the values its lane bit selects): lane fr
+    // ends with output o = fr >> 3 of rows r = 2 (fr & 7) + k, k < 2.  (The reduce-scatter is written here and in
+    // h3_ntp_body, not as a function of its own: as one, the walk's heads kernel needs scratch.)
+    template <class FULL>
+    __device__ __forceinline__ void store_heads(FULL, float *Ct, float *part, int64_t N, int64_t M, int64_t m0, int rw,
+                                                int rp, int col0, int fr, float inv, float invB,
+                                                const float (&bv)[TN], const float (&wv)[4][TN]) const {
+        static_assert(TN == 2 && WTN == 64, "heads epilogue: a wave tile 64 columns wide");
+#pragma unroll
+        for (int i = 0; i < TM; i++) {
+            float pv[64];  // [o][r]
+#pragma unroll
+            for (int q = 0; q < 64; q++) pv[q] = 0.0f;
+#pragma unroll
+            for (int j = 0; j < TN; j++) {
+                const int col = col0 + j * 32;
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int64_t row = m0 + rw + i * 32 + (r & 3) + 8 * (r >> 2);
+                    const float v = relu_nan(acc(i, j, r) * inv * invB + bv[j]);
+                    if (FULL::value || row < M) Ct[row * N + col] = v;
+#pragma unroll
+                    for (int o = 0; o < 4; o++) pv[o * 16 + r] += v * wv[o][j];
+                }
+            }
+#pragma unroll
+            for (int c = 64, off = 16; off >= 1; c >>= 1, off >>= 1) {
+                const bool up = (fr & off) != 0;
+#pragma unroll
+                for (int k = 0; k < c / 2; k++) {
+                    const float send = up ? pv[k] : pv[k + c / 2], keep = up ? pv[k + c / 2] : pv[k];
+                    pv[k] = keep + __shfl_xor(send, off);
+                }
+            }
+            const int o = fr >> 3;
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const int r = 2 * (fr & 7) + k;
+                const int64_t row = m0 + rp + i * 32 + (r & 3) + 8 * (r >> 2);
+                if (FULL::value || row < M) part[row * 4 + o] = pv[k];
+            }
+        }
+    }
+};
+
+// NS: LDS stages of the DMA ring (NS - 1 k steps in flight).  3: 120 KB at 128 x 192; 4 (round 6): 160 KB, the whole
+// LDS of a CU -- a step's DMA is latency-bound (~2.5 us under load against ~1.2 us of MFMA work per step), so the
+// feed rate per CU is the bytes in flight over that latency
 // (pq_tile: the body of k_h3_pq's one-tile form, a block per tile; the kernel and its persistent form are defined
 // behind the walks, at the end of this namespace)
 template <int BM, int BN, int WGM, int WGN, int EPI, int NK, int NS, bool ONE, int ORD>
@@ -84,20 +259,15 @@ __device__ __forceinline__ void pq_tile(const p_u32x4 *__restrict__ A, const p_u
                                         int64_t M, int N, int K, int64_t sA, int64_t sB,
                                         const float *__restrict__ bias, float *__restrict__ C, int64_t sC,
                                         int tiles_n) {
-    constexpr int NT = 64 * WGM * WGN;
-    constexpr int WTM = BM / WGM, WTN = BN / WGN;
-    constexpr int TM = WTM / 32, TN = WTN / 32;
-    constexpr int NR = 2 * (TM + TN), NM = 3 * TM * TN;  // fragment reads / MFMAs per half step
-    static_assert(NM >= NR, "a read behind every MFMA");
-    constexpr int G = (BM + BN) * 8 / NT;  // DMA instructions per thread and k step
-    static_assert((BM * 8) % NT == 0 && (BN * 8) % NT == 0, "whole DMA instructions per thread");
-    constexpr int STG = (BM + BN) * 8;  // chunks per stage
-    constexpr uint32_t STG_B = STG * 16;
+    using P = PCore<BM, BN, WGM, WGN, ONE, ORD>;
+    using Frag = typename P::Frag;
+    constexpr int NT = P::NT, WTM = P::WTM, WTN = P::WTN, TN = P::TN, NR = P::NR, G = P::G, STG = P::STG;
+    constexpr uint32_t STG_B = P::STG_B;
     static_assert(NS >= 2 && NS <= 4, "ring depth");
     __shared__ p_u32x4 lds[NS * STG];
 
     const int t = blockIdx.y;
-    const int L = p_xcd_tile(blockIdx.x, gridDim.x);
+    const int L = xcd_tile(blockIdx.x, gridDim.x);
     const int tm = L / tiles_n, tn = L - tm * tiles_n;
     const int64_t m0 = (int64_t)tm * BM;
     const int n0 = tn * BN;
@@ -106,7 +276,7 @@ __device__ __forceinline__ void pq_tile(const p_u32x4 *__restrict__ A, const p_u
     const int64_t row_ch = K / 4;  // chunks per operand row (4 B per value, planes)
 
     // the scales first: an ordinary load consumed after a DMA is issued makes the compiler wait for the DMA too
-    const int eA = p_exp(p_amax(amaxA + t)), eB = p_exp(p_amax(amaxB + t));
+    const int eA = h3_exp(load_amax(amaxA + t)), eB = h3_exp(load_amax(amaxB + t));
     // DMA sources as 32-bit chunk offsets from the uniform row-block bases (6 VGPRs, not 6 64-bit pointers): A's
     // block rows m0.. and B's n0.. (the last A rows clamped to M - 1: read, never stored)
     const p_u32x4 *baseA = A + t * sA + m0 * row_ch, *baseB = B + t * sB + (int64_t)n0 * row_ch;
@@ -128,135 +298,43 @@ __device__ __forceinline__ void pq_tile(const p_u32x4 *__restrict__ A, const p_u
         }
     };
 
-    // fragment addresses (bytes, stage 0): A tile i / B tile j at half kh, plane p -> row r, chunk 2 (2 kh + fh) + p
     const int fr = lane & 31, fh = lane >> 5;
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) p_u32x4 *)lds;
-    uint32_t adA[2][2], adB[2][2];  // [kh][p], tile 0; tile i is +32 i rows (same swizzle)
-    {
-        const int ra = wm * WTM + fr, rb = BM + wn * WTN + fr;
-#pragma unroll
-        for (int kh = 0; kh < 2; kh++)
-#pragma unroll
-            for (int p = 0; p < 2; p++) {
-                const int c = 2 * (2 * kh + fh) + p;
-                adA[kh][p] = lds0 + (uint32_t)(ra * 8 + (c ^ p_swz(ra))) * 16u;
-                adB[kh][p] = lds0 + (uint32_t)(rb * 8 + (c ^ p_swz(rb))) * 16u;
-            }
-    }
-    struct Frag {
-        p_u32x4 a[TM][2], b[TN][2];  // [tile][plane]
-    };
-    // the 8 reads of half kh of stage st, interleaved behind the 12 MFMAs on f (fenced one by one)
-    p_f32x16 hi[TM][TN], lo[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-        for (int j = 0; j < TN; j++) {
-            hi[i][j] = p_f32x16{};
-            lo[i][j] = p_f32x16{};
-        }
-    // the k-th of the NR fragment reads of half KH into g (k, KH compile-time: no runtime-indexed fragment arrays)
-    auto rd = [&](Frag &g, auto K_, uint32_t so, auto KH) __attribute__((always_inline)) {
-        constexpr int k = decltype(K_)::value, kh = decltype(KH)::value;
-        if constexpr (k < 2 * TM)
-            lds_rd(g.a[k >> 1][k & 1], adA[kh][k & 1] + so + (k >> 1) * 32 * 128);
-        else
-            lds_rd(g.b[(k - 2 * TM) >> 1][k & 1], adB[kh][k & 1] + so + ((k - 2 * TM) >> 1) * 32 * 128);
-    };
-    // MFMA m: tile (i, j), product pr -- ORD 0: a tile's three products back to back (m / 3 = tile, m % 3 = pr);
-    // ORD 1: product-major (every tile's pr 0, then every tile's pr 1, ...), so consecutive MFMAs never share an
-    // accumulator; each accumulator still sums the same products in the same order (the same bits)
-    auto mf = [&](const Frag &f, const Frag &u, auto M_) __attribute__((always_inline)) {
-        constexpr int m = decltype(M_)::value, tl = ORD ? m % (TM * TN) : m / 3, pr = ORD ? m / (TM * TN) : m % 3;
-        constexpr int i = tl / TN, j = tl % TN;
-        if constexpr (ONE) {  // u: f's lo planes at scale
-            if constexpr (pr == 0)
-                hi[i][j] = p_mfma(u.a[i][1], f.b[j][0], hi[i][j]);
-            else if constexpr (pr == 1)
-                hi[i][j] = p_mfma(f.a[i][0], u.b[j][1], hi[i][j]);
-            else
-                hi[i][j] = p_mfma(f.a[i][0], f.b[j][0], hi[i][j]);
-        } else if constexpr (pr == 0)
-            lo[i][j] = p_mfma(f.a[i][1], f.b[j][0], lo[i][j]);
-        else if constexpr (pr == 1)
-            lo[i][j] = p_mfma(f.a[i][0], f.b[j][1], lo[i][j]);
-        else
-            hi[i][j] = p_mfma(f.a[i][0], f.b[j][0], hi[i][j]);
-    };
-    // half step: the 12 MFMAs on f, with the 8 reads of g (stage offset so, half KH) one behind each of the first 8
-    // (sched_group_barrier: MFMA, read, MFMA, read, ...)
-    auto half = [&](const Frag &f, Frag &g, uint32_t so, auto KH, auto READS) __attribute__((always_inline)) {
-        Frag u;
-        if constexpr (ONE) {
-#pragma unroll
-            for (int i = 0; i < TM; i++) u.a[i][1] = p_unscale(f.a[i][1]);
-#pragma unroll
-            for (int j = 0; j < TN; j++) u.b[j][1] = p_unscale(f.b[j][1]);
-        }
-        static_for<NM>([&](auto M_) __attribute__((always_inline)) {
-            mf(f, u, M_);
-            if constexpr (decltype(READS)::value && decltype(M_)::value < NR) rd(g, M_, so, KH);
-        });
-        if constexpr (decltype(READS)::value) {
-            static_for<NR>([&](auto) __attribute__((always_inline)) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            });
-            if constexpr (NM > NR) __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto touch = [&](const Frag &f) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < TM; i++) asm volatile("" ::"v"(f.a[i][0]), "v"(f.a[i][1]));
-#pragma unroll
-        for (int j = 0; j < TN; j++) asm volatile("" ::"v"(f.b[j][0]), "v"(f.b[j][1]));
-    };
+    P c;
+    c.init(lds0, wm, wn, fr, fh);
 
     static_assert(NK >= NS - 1, "the prologue's k steps");
     constexpr int D = NS - 1;  // k steps in flight
     static_for<D>([&](auto KT) __attribute__((always_inline)) { issue(decltype(KT)::value, decltype(KT)::value); });
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G * (D - 1)) : "memory");  // step 0 landed
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
+    P::publish();
     Frag f0, f1;
-    static_for<NR>([&](auto K_) __attribute__((always_inline)) { rd(f0, K_, 0, IC<0>{}); });
+    static_for<NR>([&](auto K_) __attribute__((always_inline)) { c.rd(f0, K_, 0, IC<0>{}); });
     static_for<NK>([&](auto KT) __attribute__((always_inline)) {
         constexpr int kt = decltype(KT)::value, st = kt % NS, sn = (kt + 1) % NS;
         if constexpr (kt + D < NK) issue(kt + D, (kt + D) % NS);  // the stage read in step kt - 1
         __builtin_amdgcn_sched_barrier(0);
-        half(f0, f1, (uint32_t)st * STG_B, IC<1>{}, IC<1>{});  // MFMAs of half 0, reads of half 1
+        c.half(f0, f1, (uint32_t)st * STG_B, IC<1>{}, IC<1>{});  // MFMAs of half 0, reads of half 1
         if constexpr (kt + 1 < NK) {
-            touch(f1);  // the compiler's wait for f1 here, before the barrier
+            P::touch(f1);  // the compiler's wait for f1 here, before the barrier
             // step kt + 1 landed: the steps issued after it (up to kt + D, those that exist) may stay in flight
             constexpr int later = (NK - 1 < kt + D ? NK - 1 : kt + D) - (kt + 1);
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G * later) : "memory");
-            __builtin_amdgcn_s_barrier();  // step kt + 1 published; every wave is past its reads of step kt - 1
-            __builtin_amdgcn_sched_barrier(0);
-            half(f1, f0, (uint32_t)sn * STG_B, IC<0>{}, IC<1>{});  // MFMAs of half 1, reads of the next half 0
+            P::publish();  // step kt + 1 published; every wave is past its reads of step kt - 1
+            c.half(f1, f0, (uint32_t)sn * STG_B, IC<0>{}, IC<1>{});  // MFMAs of half 1, reads of the next half 0
         } else {
-            half(f1, f0, 0u, IC<0>{}, IC<0>{});
+            c.half(f1, f0, 0u, IC<0>{}, IC<0>{});
         }
     });
 
-    const float inv = p_pow2(-eA), invB = p_pow2(-eB);
-    float *Ct = C + t * sC;
-#pragma unroll
-    for (int j = 0; j < TN; j++) {
-        const int col = n0 + wn * WTN + j * 32 + fr;
-        const float bv = EPI == 1 ? bias[(int64_t)t * N + col] : 0.0f;
-#pragma unroll
-        for (int i = 0; i < TM; i++) {
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int64_t row = m0 + wm * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                if (row < M) {
-                    const float v = (ONE ? hi[i][j][r] : hi[i][j][r] + lo[i][j][r] * P_LO_INV) * inv * invB;
-                    Ct[row * N + col] = EPI == 1 ? p_relu(v + bv) : v;
-                }
-            }
-        }
-    }
+    // (the epilogue's loads by static_for: behind a loop that does not use the accumulators the optimiser would move
+    // the hi MFMAs of every k step, which nothing in the k steps reads, out of the schedule above to this place)
+    const int col0 = n0 + wn * WTN + fr;
+    float bv[TN];
+    static_for<TN>([&](auto J) __attribute__((always_inline)) {
+        bv[decltype(J)::value] = EPI == 1 ? bias[(int64_t)t * N + col0 + decltype(J)::value * 32] : 0.0f;
+    });
+    c.store(IC<0>{}, IC<EPI>{}, C + t * sC, N, M, m0, wm * WTM + 4 * fh, col0, pow2f(-eA), pow2f(-eB), bv);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -329,12 +407,12 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tq(const p_u32x4 *__restr
     __shared__ p_u32x4 lds[3 * STG];
     __shared__ int32_t ixr[3 * XS];
 
-    const int P = p_xcd_tile(blockIdx.x, gridDim.x);
+    const int P = xcd_tile(blockIdx.x, gridDim.x);
     const int t = P / (S * tiles), s = (P / tiles) % S, Lt = P % tiles;
     const int tm = Lt / tiles_n, tn = Lt - tm * tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
     const int64_t k0 = (int64_t)s * kc, k1 = std::min<int64_t>(Kd, k0 + kc);
-    const int eA = p_exp(p_amax(amaxA + t)), eB = p_exp(p_amax(amaxB + t));
+    const int eA = h3_exp(load_amax(amaxA + t)), eB = h3_exp(load_amax(amaxB + t));
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int wm = w / WGN, wn = w - (w / WGN) * WGN;
     const int nc = N / 64, j0 = n0 / 64;
@@ -499,7 +577,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tq(const p_u32x4 *__restr
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the padded steps' DMAs drained before the block ends
 
-    const float inv = p_pow2(-eA), invB = p_pow2(-eB);
+    const float inv = pow2f(-eA), invB = pow2f(-eB);
     float *St = slab + ((int64_t)s * (gridDim.x / (S * tiles)) + t) * (int64_t)M * N;
     const int fr = lane & 31, fh = lane >> 5;
 #pragma unroll
@@ -509,7 +587,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tq(const p_u32x4 *__restr
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 const int row = m0 + wm * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                St[(int64_t)row * N + n0 + wn * WTN + j * 32 + fr] = (hi[i][j][r] + lo[i][j][r] * P_LO_INV) * inv * invB;
+                St[(int64_t)row * N + n0 + wn * WTN + j * 32 + fr] = (hi[i][j][r] + lo[i][j][r] * H3_LO_INV) * inv * invB;
             }
 }
 
@@ -531,26 +609,22 @@ __device__ __forceinline__ void pqg_tile(const p_u32x4 *__restrict__ A, const p_
                                          const int32_t *__restrict__ amap, const float *__restrict__ hw0,
                                          const float *__restrict__ hw1, int na, float *__restrict__ hpart) {
     constexpr int K = 576, NK = 18, KC = K / 64;
-    constexpr int NT = 64 * WGM * WGN;
-    constexpr int WTM = BM / WGM, WTN = BN / WGN;
-    constexpr int TM = WTM / 32, TN = WTN / 32;
-    constexpr int NR = 2 * (TM + TN), NM = 3 * TM * TN;
-    static_assert(NM >= NR, "a read behind every MFMA");
-    constexpr int GA = BM * 8 / NT, GB = BN * 8 / NT, G = GA + GB;
-    static_assert((BM * 8) % NT == 0 && (BN * 8) % NT == 0, "whole DMA instructions per thread");
-    constexpr int STG = (BM + BN) * 8;
-    constexpr uint32_t STG_B = STG * 16;
+    using P = PCore<BM, BN, WGM, WGN>;
+    using Frag = typename P::Frag;
+    constexpr int NT = P::NT, WTM = P::WTM, WTN = P::WTN, TN = P::TN, NR = P::NR, GA = P::GA, GB = P::GB, G = P::G;
+    constexpr int STG = P::STG;
+    constexpr uint32_t STG_B = P::STG_B;
     __shared__ p_u32x4 lds[3 * STG];
     __shared__ int32_t gmap[BM * KC];
 
     const int t = blockIdx.y;
-    const int L = p_xcd_tile(blockIdx.x, gridDim.x);
+    const int L = xcd_tile(blockIdx.x, gridDim.x);
     const int tm = L / tiles_n, tn = L - tm * tiles_n;
     const int64_t m0 = (int64_t)tm * BM;
     const int n0 = tn * BN;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int wm = w / WGN, wn = w - (w / WGN) * WGN;
-    const int eA = p_exp(p_amax(amaxA + t)), eB = p_exp(p_amax(amaxB + t));
+    const int eA = h3_exp(load_amax(amaxA + t)), eB = h3_exp(load_amax(amaxB + t));
     for (int e = tid; e < BM * KC; e += NT) {
         const int r = e / KC;
         gmap[e] = amap[std::min<int64_t>(m0 + r, M - 1) * KC + (e - r * KC)];
@@ -589,65 +663,8 @@ __device__ __forceinline__ void pqg_tile(const p_u32x4 *__restrict__ A, const p_
     };
 
     const int fr = lane & 31, fh = lane >> 5;
-    uint32_t adA[2][2], adB[2][2];
-    {
-        const int ra = wm * WTM + fr, rb = BM + wn * WTN + fr;
-#pragma unroll
-        for (int kh = 0; kh < 2; kh++)
-#pragma unroll
-            for (int p = 0; p < 2; p++) {
-                const int c = 2 * (2 * kh + fh) + p;
-                adA[kh][p] = lds0 + (uint32_t)(ra * 8 + (c ^ p_swz(ra))) * 16u;
-                adB[kh][p] = lds0 + (uint32_t)(rb * 8 + (c ^ p_swz(rb))) * 16u;
-            }
-    }
-    struct Frag {
-        p_u32x4 a[TM][2], b[TN][2];
-    };
-    p_f32x16 hi[TM][TN], lo[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-        for (int j = 0; j < TN; j++) {
-            hi[i][j] = p_f32x16{};
-            lo[i][j] = p_f32x16{};
-        }
-    auto rd = [&](Frag &g, auto K_, uint32_t so, auto KH) __attribute__((always_inline)) {
-        constexpr int k = decltype(K_)::value, kh = decltype(KH)::value;
-        if constexpr (k < 2 * TM)
-            lds_rd(g.a[k >> 1][k & 1], adA[kh][k & 1] + so + (k >> 1) * 32 * 128);
-        else
-            lds_rd(g.b[(k - 2 * TM) >> 1][k & 1], adB[kh][k & 1] + so + ((k - 2 * TM) >> 1) * 32 * 128);
-    };
-    auto mf = [&](const Frag &f, auto M_) __attribute__((always_inline)) {
-        constexpr int m = decltype(M_)::value, i = m / (3 * TN), j = (m / 3) % TN, pr = m % 3;
-        if constexpr (pr == 0)
-            lo[i][j] = p_mfma(f.a[i][1], f.b[j][0], lo[i][j]);
-        else if constexpr (pr == 1)
-            lo[i][j] = p_mfma(f.a[i][0], f.b[j][1], lo[i][j]);
-        else
-            hi[i][j] = p_mfma(f.a[i][0], f.b[j][0], hi[i][j]);
-    };
-    auto half = [&](const Frag &f, Frag &g, uint32_t so, auto KH, auto READS) __attribute__((always_inline)) {
-        static_for<NM>([&](auto M_) __attribute__((always_inline)) {
-            mf(f, M_);
-            if constexpr (decltype(READS)::value && decltype(M_)::value < NR) rd(g, M_, so, KH);
-        });
-        if constexpr (decltype(READS)::value) {
-            static_for<NR>([&](auto) __attribute__((always_inline)) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            });
-            if constexpr (NM > NR) __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto touch = [&](const Frag &f) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < TM; i++) asm volatile("" ::"v"(f.a[i][0]), "v"(f.a[i][1]));
-#pragma unroll
-        for (int j = 0; j < TN; j++) asm volatile("" ::"v"(f.b[j][0]), "v"(f.b[j][1]));
-    };
+    P c;
+    c.init(lds0, wm, wn, fr, fh);
 
     int32_t g0[GA], g1[GA];  // chunk rows of the next issue (ping-pong, compile-time choice)
     read_g(0, g0);
@@ -656,109 +673,57 @@ __device__ __forceinline__ void pqg_tile(const p_u32x4 *__restrict__ A, const p_
     issue(1, 1, g1);
     read_g(2, g0);
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G) : "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
+    P::publish();
     Frag f0, f1;
-    static_for<NR>([&](auto K_) __attribute__((always_inline)) { rd(f0, K_, 0, IC<0>{}); });
+    static_for<NR>([&](auto K_) __attribute__((always_inline)) { c.rd(f0, K_, 0, IC<0>{}); });
     static_for<NK>([&](auto KT) __attribute__((always_inline)) {
         constexpr int kt = decltype(KT)::value, st = kt % 3, sn = (kt + 1) % 3;
         int32_t(&gu)[GA] = (kt % 2 == 0) ? g0 : g1;  // holds step kt + 2's rows
         int32_t(&gn)[GA] = (kt % 2 == 0) ? g1 : g0;
         if constexpr (kt + 2 < NK) issue(kt + 2, (kt + 2) % 3, gu);
         __builtin_amdgcn_sched_barrier(0);
-        half(f0, f1, (uint32_t)st * STG_B, IC<1>{}, IC<1>{});
+        c.half(f0, f1, (uint32_t)st * STG_B, IC<1>{}, IC<1>{});
         if constexpr (kt + 1 < NK) {
-            touch(f1);
+            P::touch(f1);
             if constexpr (kt + 2 < NK)
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G) : "memory");
             else
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
+            P::publish();
             if constexpr (kt + 3 < NK) read_g(kt + 3, gn);
-            half(f1, f0, (uint32_t)sn * STG_B, IC<0>{}, IC<1>{});
+            c.half(f1, f0, (uint32_t)sn * STG_B, IC<0>{}, IC<1>{});
         } else {
-            half(f1, f0, 0u, IC<0>{}, IC<0>{});
+            c.half(f1, f0, 0u, IC<0>{}, IC<0>{});
         }
     });
 
-    const float inv = p_pow2(-eA), invB = p_pow2(-eB);
+    const float inv = pow2f(-eA), invB = pow2f(-eB);
     float *Ct = C + t * sC;
-    if constexpr (EPI == 2) {  // k_h3_ntp's heads epilogue (merlin_h3.hip h3_ntp_body EPI 2)
-        static_assert(TN == 2 && WTN == 64, "heads epilogue: a wave tile 64 columns wide");
+    const int col0 = n0 + wn * WTN + fr, rw = wm * WTM + 4 * fh;
+    float bv[TN];
+    static_for<TN>([&](auto J) __attribute__((always_inline)) {
+        bv[decltype(J)::value] = EPI >= 1 ? bias[(int64_t)t * N + col0 + decltype(J)::value * 32] : 0.0f;
+    });
+    if constexpr (EPI == 2) {
         const float *hw = t == 0 ? hw0 : hw1;
         const int nh = t == 0 ? na : 1;
-        float wv[4][TN], bv[TN];
-#pragma unroll
-        for (int j = 0; j < TN; j++) {
-            const int col = n0 + wn * WTN + j * 32 + fr;
-            bv[j] = bias[(int64_t)t * N + col];
-#pragma unroll
-            for (int o = 0; o < 4; o++) {  // loaded unconditionally (row clamped into [0, nh)): no load behind a branch
-                const float x = hw[(int64_t)(o < nh ? o : 0) * N + col];
-                wv[o][j] = o < nh ? x : 0.0f;
-            }
-        }
+        float wv[4][TN];
+        static_for<4 * TN>([&](auto Q) __attribute__((always_inline)) {
+            constexpr int j = decltype(Q)::value / 4, o = decltype(Q)::value % 4;
+            // loaded unconditionally (row clamped into [0, nh)): no load behind a branch
+            const float x = hw[(int64_t)(o < nh ? o : 0) * N + col0 + j * 32];
+            wv[o][j] = o < nh ? x : 0.0f;
+        });
         float *part = hpart + ((int64_t)(t * tiles_n + tn) * WGN + wn) * M * 4;
-#pragma unroll
-        for (int i = 0; i < TM; i++) {
-            float pv[64];
-#pragma unroll
-            for (int q = 0; q < 64; q++) pv[q] = 0.0f;
-#pragma unroll
-            for (int j = 0; j < TN; j++) {
-                const int col = n0 + wn * WTN + j * 32 + fr;
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int64_t row = m0 + wm * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                    const float v = p_relu((hi[i][j][r] + lo[i][j][r] * P_LO_INV) * inv * invB + bv[j]);
-                    if (row < M) Ct[row * N + col] = v;
-#pragma unroll
-                    for (int o = 0; o < 4; o++) pv[o * 16 + r] += v * wv[o][j];
-                }
-            }
-#pragma unroll
-            for (int c = 64, off = 16; off >= 1; c >>= 1, off >>= 1) {
-                const bool up = (fr & off) != 0;
-#pragma unroll
-                for (int k = 0; k < c / 2; k++) {
-                    const float send = up ? pv[k] : pv[k + c / 2], keep = up ? pv[k + c / 2] : pv[k];
-                    pv[k] = keep + __shfl_xor(send, off);
-                }
-            }
-            const int o = fr >> 3;
-#pragma unroll
-            for (int k = 0; k < 2; k++) {
-                const int r = 2 * (fr & 7) + k;
-                const int64_t row = m0 + wm * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                if (row < M) part[row * 4 + o] = pv[k];
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < TN; j++) {
-        const int col = n0 + wn * WTN + j * 32 + fr;
-        const float bv = EPI == 1 ? bias[(int64_t)t * N + col] : 0.0f;
-#pragma unroll
-        for (int i = 0; i < TM; i++) {
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int64_t row = m0 + wm * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                if (row < M) {
-                    const float v = (hi[i][j][r] + lo[i][j][r] * P_LO_INV) * inv * invB;
-                    Ct[row * N + col] = EPI == 1 ? p_relu(v + bv) : v;
-                }
-            }
-        }
+        c.store_heads(IC<0>{}, Ct, part, N, M, m0, rw, rw, col0, fr, inv, invB, bv, wv);
+    } else {
+        c.store(IC<0>{}, IC<EPI>{}, Ct, N, M, m0, rw, col0, inv, invB, bv);
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Persistent forms of the two NT kernels above (k_h3_pq / k_h3_pqg with PERS): at most one block per CU, each
-// walking a static list of (tower, tile) items -- item p_xcd_tile(b + i gridDim.x, T x tiles) of the tower-major
+// walking a static list of (tower, tile) items -- item xcd_tile(b + i gridDim.x, T x tiles) of the tower-major
 // list for block b's i-th tile, so the blocks of one XCD still work on neighbouring tiles at the same time.  No
 // block talks to another: no counters, nothing to spin on.
 // The DMA ring runs on across tile boundaries: the last two k steps of a tile issue the first two of the block's
@@ -797,7 +762,7 @@ struct PItem {
     int64_t m0;
 };
 __device__ __forceinline__ PItem p_item(int v, int W, int tiles, int tiles_n, int BM, int BN) {
-    const int it = p_xcd_tile(v, W), t = it / tiles, L = it - t * tiles, tm = L / tiles_n, tn = L - tm * tiles_n;
+    const int it = xcd_tile(v, W), t = it / tiles, L = it - t * tiles, tm = L / tiles_n, tn = L - tm * tiles_n;
     return PItem{t, tn * BN, tn, (int64_t)tm * BM};
 }
 
@@ -807,16 +772,12 @@ __device__ __forceinline__ void pq_walk(const p_u32x4 *__restrict__ A, const p_u
                                         int64_t M, int N, int K, int64_t sA, int64_t sB,
                                         const float *__restrict__ bias, float *__restrict__ C, int64_t sC,
                                         int tiles_n, int tiles, int W) {
-    constexpr int NT = 64 * WGM * WGN;
-    constexpr int WTM = BM / WGM, WTN = BN / WGN;
-    constexpr int TM = WTM / 32, TN = WTN / 32;
-    constexpr int NR = 2 * (TM + TN), NM = 3 * TM * TN;
-    static_assert(NM >= NR, "a read behind every MFMA");
-    static_assert((BM * 8) % NT == 0 && (BN * 8) % NT == 0, "whole DMA instructions per thread");
-    constexpr int GA = BM * 8 / NT, GB = BN * 8 / NT, G = GA + GB;
-    constexpr int STG = (BM + BN) * 8;
-    constexpr uint32_t STG_B = STG * 16;
-    constexpr int S = TM * TN * 16;               // C stores per wave and tile
+    using P = PCore<BM, BN, WGM, WGN, false, ORD>;
+    using Frag = typename P::Frag;
+    constexpr int NT = P::NT, WTM = P::WTM, WTN = P::WTN, TN = P::TN, NR = P::NR, GA = P::GA, GB = P::GB, G = P::G;
+    constexpr int STG = P::STG;
+    constexpr uint32_t STG_B = P::STG_B;
+    constexpr int S = P::CS;                        // C stores per wave and tile
     constexpr int CARRY = S + G < 63 ? S + G : 63;  // the vmcnt field's largest value
     const int N_ = N;
     static_assert(NK >= 4, "the look-ahead's k steps");
@@ -834,7 +795,7 @@ __device__ __forceinline__ void pq_walk(const p_u32x4 *__restrict__ A, const p_u
     PItem cur = p_item(v, W, tiles, tiles_n, BM, BN);
     // the epilogue's constants of the item they were loaded for
     int lt = cur.t, ln = cur.n0;
-    int eA = p_exp(p_amax(amaxA + lt)), eB = p_exp(p_amax(amaxB + lt));
+    int eA = h3_exp(load_amax(amaxA + lt)), eB = h3_exp(load_amax(amaxB + lt));
     float bvv[TN];
     const int fr = lane & 31, fh = lane >> 5;
 #pragma unroll
@@ -871,116 +832,35 @@ __device__ __forceinline__ void pq_walk(const p_u32x4 *__restrict__ A, const p_u
         for (int i = 0; i < GB; i++) p_dma16s(bB + kt * 8, offB[i], base + (uint32_t)((GA + i) * NT) * 16u);
     };
 
-    uint32_t adA[2][2], adB[2][2];
-    {
-        const int ra = wm * WTM + fr, rb = BM + wn * WTN + fr;
-#pragma unroll
-        for (int kh = 0; kh < 2; kh++)
-#pragma unroll
-            for (int p = 0; p < 2; p++) {
-                const int c = 2 * (2 * kh + fh) + p;
-                adA[kh][p] = lds0 + (uint32_t)(ra * 8 + (c ^ p_swz(ra))) * 16u;
-                adB[kh][p] = lds0 + (uint32_t)(rb * 8 + (c ^ p_swz(rb))) * 16u;
-            }
-    }
-    struct Frag {
-        p_u32x4 a[TM][2], b[TN][2];
-    };
-    p_f32x16 hi[TM][TN], lo[TM][TN];
-    auto zero = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < TM; i++)
-#pragma unroll
-            for (int j = 0; j < TN; j++) {
-                hi[i][j] = p_f32x16{};
-                lo[i][j] = p_f32x16{};
-            }
-    };
-    zero();
-    auto rd = [&](Frag &g, auto K_, uint32_t so, auto KH) __attribute__((always_inline)) {
-        constexpr int k = decltype(K_)::value, kh = decltype(KH)::value;
-        if constexpr (k < 2 * TM)
-            lds_rd(g.a[k >> 1][k & 1], adA[kh][k & 1] + so + (k >> 1) * 32 * 128);
-        else
-            lds_rd(g.b[(k - 2 * TM) >> 1][k & 1], adB[kh][k & 1] + so + ((k - 2 * TM) >> 1) * 32 * 128);
-    };
-    auto mf = [&](const Frag &f, auto M_) __attribute__((always_inline)) {  // k_h3_pq's orders
-        constexpr int m = decltype(M_)::value, tl = ORD ? m % (TM * TN) : m / 3, pr = ORD ? m / (TM * TN) : m % 3;
-        constexpr int i = tl / TN, j = tl % TN;
-        if constexpr (pr == 0)
-            lo[i][j] = p_mfma(f.a[i][1], f.b[j][0], lo[i][j]);
-        else if constexpr (pr == 1)
-            lo[i][j] = p_mfma(f.a[i][0], f.b[j][1], lo[i][j]);
-        else
-            hi[i][j] = p_mfma(f.a[i][0], f.b[j][0], hi[i][j]);
-    };
-    auto half = [&](const Frag &f, Frag &g, uint32_t so, auto KH, auto READS) __attribute__((always_inline)) {
-        static_for<NM>([&](auto M_) __attribute__((always_inline)) {
-            mf(f, M_);
-            if constexpr (decltype(READS)::value && decltype(M_)::value < NR) rd(g, M_, so, KH);
-        });
-        if constexpr (decltype(READS)::value) {
-            static_for<NR>([&](auto) __attribute__((always_inline)) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            });
-            if constexpr (NM > NR) __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto touch = [&](const Frag &f) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < TM; i++) asm volatile("" ::"v"(f.a[i][0]), "v"(f.a[i][1]));
-#pragma unroll
-        for (int j = 0; j < TN; j++) asm volatile("" ::"v"(f.b[j][0]), "v"(f.b[j][1]));
-    };
-    auto publish = [&]() __attribute__((always_inline)) {
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-    };
+    P c;
+    c.init(lds0, wm, wn, fr, fh);
     auto store_tile = [&](auto FULL) __attribute__((always_inline)) {
-        const float inv = p_pow2(-eA), invB = p_pow2(-eB);
-        float *Ct = C + cur.t * sC;
         // opaque per tile: the 48 store addresses are made here, not hoisted out of the walk and kept (or spilled)
         int64_t N = N_;
         int rw = wm * WTM + 4 * fh;
         asm volatile("" : "+s"(N), "+v"(rw));
-#pragma unroll
-        for (int j = 0; j < TN; j++) {
-            const int col = cur.n0 + wn * WTN + j * 32 + fr;
-#pragma unroll
-            for (int i = 0; i < TM; i++) {
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int64_t row = cur.m0 + rw + i * 32 + (r & 3) + 8 * (r >> 2);
-                    if (decltype(FULL)::value || row < M) {
-                        const float x = (hi[i][j][r] + lo[i][j][r] * P_LO_INV) * inv * invB;
-                        Ct[row * N + col] = EPI == 1 ? p_relu(x + bvv[j]) : x;
-                    }
-                }
-            }
-        }
+        c.store(FULL, IC<EPI>{}, C + cur.t * sC, N, M, cur.m0, rw, cur.n0 + wn * WTN + fr, pow2f(-eA), pow2f(-eB),
+                bvv);
     };
 
     set_base(cur);
     issue(IC<0>{}, sv[0]);
     issue(IC<1>{}, sv[1]);
     P_VMCNT(G);  // step 0 landed
-    publish();
+    P::publish();
     bool carried = false;  // the previous tile's C stores may still be in flight
     for (;;) {
         const bool more = v + nb < W;
         const PItem nxt = more ? p_item(v + nb, W, tiles, tiles_n, BM, BN) : cur;
         Frag f0, f1;
-        static_for<NR>([&](auto K_) __attribute__((always_inline)) { rd(f0, K_, sv[0], IC<0>{}); });
+        static_for<NR>([&](auto K_) __attribute__((always_inline)) { c.rd(f0, K_, sv[0], IC<0>{}); });
         static_for<NK>([&](auto KT) __attribute__((always_inline)) {
             constexpr int kt = decltype(KT)::value, st = kt % 3, sn = (kt + 1) % 3, s2 = (kt + 2) % 3;
             if constexpr (kt == NK - 2) set_base(nxt);  // from here on the DMAs are the next item's
             issue(IC<(kt + 2) % NK>{}, sv[s2]);         // the stage read in step kt - 1
             __builtin_amdgcn_sched_barrier(0);
-            half(f0, f1, sv[st], IC<1>{}, IC<1>{});
-            touch(f1);
+            c.half(f0, f1, sv[st], IC<1>{}, IC<1>{});
+            P::touch(f1);
             // step kt + 1 landed: the step just issued may stay in flight, and behind the first step of a tile the
             // stores of the tile before it, which were issued between the two
             if constexpr (kt == 0) {
@@ -991,15 +871,15 @@ __device__ __forceinline__ void pq_walk(const p_u32x4 *__restrict__ A, const p_u
             } else {
                 P_VMCNT(G);
             }
-            publish();  // step kt + 1 published; every wave is past its reads of step kt - 1
+            P::publish();  // step kt + 1 published; every wave is past its reads of step kt - 1
             if constexpr (kt + 1 < NK)
-                half(f1, f0, sv[sn], IC<0>{}, IC<1>{});
+                c.half(f1, f0, sv[sn], IC<0>{}, IC<1>{});
             else
-                half(f1, f0, 0u, IC<0>{}, IC<0>{});
+                c.half(f1, f0, 0u, IC<0>{}, IC<0>{});
         });
         if (cur.t != lt || (EPI == 1 && cur.n0 != ln)) {
             lt = cur.t, ln = cur.n0;
-            eA = p_exp(p_amax(amaxA + lt)), eB = p_exp(p_amax(amaxB + lt));
+            eA = h3_exp(load_amax(amaxA + lt)), eB = h3_exp(load_amax(amaxB + lt));
 #pragma unroll
             for (int j = 0; j < TN; j++)
                 bvv[j] = EPI == 1 ? bias[(int64_t)lt * N + ln + wn * WTN + j * 32 + fr] : 0.0f;
@@ -1012,7 +892,7 @@ __device__ __forceinline__ void pq_walk(const p_u32x4 *__restrict__ A, const p_u
             store_tile(IC<0>{});
             P_VMCNT(0);
         }
-        zero();
+        c.zero();
         if (!more) break;
         v += nb;
         cur = nxt;
@@ -1038,21 +918,16 @@ __device__ __forceinline__ void pqg_walk(const p_u32x4 *__restrict__ A, const p_
                                          const int32_t *__restrict__ amap, const float *__restrict__ hw0,
                                          const float *__restrict__ hw1, int na, float *__restrict__ hpart) {
     constexpr int K = 576, NK = 18, KC = K / 64;
-    constexpr int NT = 64 * WGM * WGN;
-    constexpr int WTM = BM / WGM, WTN = BN / WGN;
-    constexpr int TM = WTM / 32, TN = WTN / 32;
-    constexpr int NR = 2 * (TM + TN), NM = 3 * TM * TN;
-    static_assert(NM >= NR, "a read behind every MFMA");
-    static_assert((BM * 8) % NT == 0 && (BN * 8) % NT == 0, "whole DMA instructions per thread");
-    constexpr int GA = BM * 8 / NT, GB = BN * 8 / NT, G = GA + GB;
+    using P = PCore<BM, BN, WGM, WGN>;
+    using Frag = typename P::Frag;
+    constexpr int NT = P::NT, WTM = P::WTM, WTN = P::WTN, TM = P::TM, TN = P::TN, NR = P::NR, GA = P::GA, GB = P::GB;
+    constexpr int G = P::G, STG = P::STG;
+    constexpr uint32_t STG_B = P::STG_B;
     constexpr int GX = (BM * KC + NT - 1) / NT, XS = GX * NT;  // row map DMAs per thread; ints per buffer
-    constexpr int STG = (BM + BN) * 8;
-    constexpr uint32_t STG_B = STG * 16;
-    constexpr int S = TM * TN * 16 + (EPI == 2 ? 2 * TM : 0);  // stores per wave and tile
+    constexpr int S = P::CS + (EPI == 2 ? 2 * TM : 0);         // stores per wave and tile
     constexpr int CARRY = S + G < 63 ? S + G : 63;
     const int N_ = N;
     static_assert(EPI == 1 || EPI == 2, "bias + ReLU, heads optional");
-    static_assert(EPI != 2 || (TN == 2 && WTN == 64), "heads epilogue: a wave tile 64 columns wide");
     __shared__ p_u32x4 lds[3 * STG];
     __shared__ int32_t gmap[2 * XS];
 
@@ -1071,7 +946,7 @@ __device__ __forceinline__ void pqg_walk(const p_u32x4 *__restrict__ A, const p_
     float bvv[TN], wv[4][TN];
     auto load_consts = [&]() __attribute__((always_inline)) {  // (k_h3_pqg's epilogue loads)
         lt = cur.t, ln = cur.n0;
-        eA = p_exp(p_amax(amaxA + lt)), eB = p_exp(p_amax(amaxB + lt));
+        eA = h3_exp(load_amax(amaxA + lt)), eB = h3_exp(load_amax(amaxB + lt));
         const float *hw = lt == 0 ? hw0 : hw1;
         const int nh = lt == 0 ? na : 1;
 #pragma unroll
@@ -1140,141 +1015,29 @@ __device__ __forceinline__ void pqg_walk(const p_u32x4 *__restrict__ A, const p_
         for (int i = 0; i < GB; i++) p_dma16s(baseB + kt * 8, offB[i], base + (uint32_t)((GA + i) * NT) * 16u);
     };
 
-    uint32_t adA[2][2], adB[2][2];
-    {
-        const int ra = wm * WTM + fr, rb = BM + wn * WTN + fr;
-#pragma unroll
-        for (int kh = 0; kh < 2; kh++)
-#pragma unroll
-            for (int p = 0; p < 2; p++) {
-                const int c = 2 * (2 * kh + fh) + p;
-                adA[kh][p] = lds0 + (uint32_t)(ra * 8 + (c ^ p_swz(ra))) * 16u;
-                adB[kh][p] = lds0 + (uint32_t)(rb * 8 + (c ^ p_swz(rb))) * 16u;
-            }
-    }
-    struct Frag {
-        p_u32x4 a[TM][2], b[TN][2];
-    };
-    p_f32x16 hi[TM][TN], lo[TM][TN];
-    auto zero = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < TM; i++)
-#pragma unroll
-            for (int j = 0; j < TN; j++) {
-                hi[i][j] = p_f32x16{};
-                lo[i][j] = p_f32x16{};
-            }
-    };
-    zero();
-    auto rd = [&](Frag &g, auto K_, uint32_t so, auto KH) __attribute__((always_inline)) {
-        constexpr int k = decltype(K_)::value, kh = decltype(KH)::value;
-        if constexpr (k < 2 * TM)
-            lds_rd(g.a[k >> 1][k & 1], adA[kh][k & 1] + so + (k >> 1) * 32 * 128);
-        else
-            lds_rd(g.b[(k - 2 * TM) >> 1][k & 1], adB[kh][k & 1] + so + ((k - 2 * TM) >> 1) * 32 * 128);
-    };
-    auto mf = [&](const Frag &f, auto M_) __attribute__((always_inline)) {
-        constexpr int m = decltype(M_)::value, i = m / (3 * TN), j = (m / 3) % TN, pr = m % 3;
-        if constexpr (pr == 0)
-            lo[i][j] = p_mfma(f.a[i][1], f.b[j][0], lo[i][j]);
-        else if constexpr (pr == 1)
-            lo[i][j] = p_mfma(f.a[i][0], f.b[j][1], lo[i][j]);
-        else
-            hi[i][j] = p_mfma(f.a[i][0], f.b[j][0], hi[i][j]);
-    };
-    auto half = [&](const Frag &f, Frag &g, uint32_t so, auto KH, auto READS) __attribute__((always_inline)) {
-        static_for<NM>([&](auto M_) __attribute__((always_inline)) {
-            mf(f, M_);
-            if constexpr (decltype(READS)::value && decltype(M_)::value < NR) rd(g, M_, so, KH);
-        });
-        if constexpr (decltype(READS)::value) {
-            static_for<NR>([&](auto) __attribute__((always_inline)) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            });
-            if constexpr (NM > NR) __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto touch = [&](const Frag &f) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < TM; i++) asm volatile("" ::"v"(f.a[i][0]), "v"(f.a[i][1]));
-#pragma unroll
-        for (int j = 0; j < TN; j++) asm volatile("" ::"v"(f.b[j][0]), "v"(f.b[j][1]));
-    };
-    auto publish = [&]() __attribute__((always_inline)) {
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-    };
+    P c;
+    c.init(lds0, wm, wn, fr, fh);
     // k_h3_pqg's epilogues on the item cur
     auto store_tile = [&](auto FULL) __attribute__((always_inline)) {
-        constexpr bool full = decltype(FULL)::value;
-        const float inv = p_pow2(-eA), invB = p_pow2(-eB);
+        const float inv = pow2f(-eA), invB = pow2f(-eB);
         float *Ct = C + cur.t * sC;
-        const int64_t m0 = cur.m0;
-        const int n0 = cur.n0;
+        const int col0 = cur.n0 + wn * WTN + fr;
         // opaque per tile: the store addresses are made here, not hoisted out of the walk and kept (or spilled)
         int64_t N = N_;
         int rw = wm * WTM + 4 * fh, rp = wm * WTM + 4 * fh;
         asm volatile("" : "+s"(N), "+v"(rw), "+v"(rp));
         if constexpr (EPI == 2) {
             float *part = hpart + ((int64_t)(cur.t * tiles_n + cur.tn) * WGN + wn) * M * 4;
-#pragma unroll
-            for (int i = 0; i < TM; i++) {
-                float pv[64];
-#pragma unroll
-                for (int q = 0; q < 64; q++) pv[q] = 0.0f;
-#pragma unroll
-                for (int j = 0; j < TN; j++) {
-                    const int col = n0 + wn * WTN + j * 32 + fr;
-#pragma unroll
-                    for (int r = 0; r < 16; r++) {
-                        const int64_t row = m0 + rw + i * 32 + (r & 3) + 8 * (r >> 2);
-                        const float x = p_relu((hi[i][j][r] + lo[i][j][r] * P_LO_INV) * inv * invB + bvv[j]);
-                        if (full || row < M) Ct[row * N + col] = x;
-#pragma unroll
-                        for (int o = 0; o < 4; o++) pv[o * 16 + r] += x * wv[o][j];
-                    }
-                }
-#pragma unroll
-                for (int c = 64, off = 16; off >= 1; c >>= 1, off >>= 1) {
-                    const bool up = (fr & off) != 0;
-#pragma unroll
-                    for (int k = 0; k < c / 2; k++) {
-                        const float send = up ? pv[k] : pv[k + c / 2], keep = up ? pv[k + c / 2] : pv[k];
-                        pv[k] = keep + __shfl_xor(send, off);
-                    }
-                }
-                const int o = fr >> 3;
-#pragma unroll
-                for (int k = 0; k < 2; k++) {
-                    const int r = 2 * (fr & 7) + k;
-                    const int64_t row = m0 + rp + i * 32 + (r & 3) + 8 * (r >> 2);
-                    if (full || row < M) part[row * 4 + o] = pv[k];
-                }
-            }
+            c.store_heads(FULL, Ct, part, N, M, cur.m0, rw, rp, col0, fr, inv, invB, bvv, wv);
         } else {
-#pragma unroll
-            for (int j = 0; j < TN; j++) {
-                const int col = n0 + wn * WTN + j * 32 + fr;
-#pragma unroll
-                for (int i = 0; i < TM; i++) {
-#pragma unroll
-                    for (int r = 0; r < 16; r++) {
-                        const int64_t row = m0 + rw + i * 32 + (r & 3) + 8 * (r >> 2);
-                        if (full || row < M)
-                            Ct[row * N + col] = p_relu((hi[i][j][r] + lo[i][j][r] * P_LO_INV) * inv * invB + bvv[j]);
-                    }
-                }
-            }
+            c.store(FULL, IC<1>{}, Ct, N, M, cur.m0, rw, col0, inv, invB, bvv);
         }
     };
 
     int cb = 0;  // the row map buffer of the item cur
     issue_map(cur.m0, cb);
     P_VMCNT(0);
-    publish();
+    P::publish();
     set_base(cur);
     uint32_t g0[GA], g1[GA];  // A sources of the next issue (ping-pong, compile-time choice: NK is even)
     read_g(0, g0, cb);
@@ -1283,13 +1046,13 @@ __device__ __forceinline__ void pqg_walk(const p_u32x4 *__restrict__ A, const p_
     issue(IC<1>{}, 1, g1);
     read_g(2, g0, cb);
     P_VMCNT(G);
-    publish();
+    P::publish();
     bool carried = false;
     for (;;) {
         const bool more = v + nb < W;
         const PItem nxt = more ? p_item(v + nb, W, tiles, tiles_n, BM, BN) : cur;
         Frag f0, f1;
-        static_for<NR>([&](auto K_) __attribute__((always_inline)) { rd(f0, K_, 0, IC<0>{}); });
+        static_for<NR>([&](auto K_) __attribute__((always_inline)) { c.rd(f0, K_, 0, IC<0>{}); });
         static_for<NK>([&](auto KT) __attribute__((always_inline)) {
             constexpr int kt = decltype(KT)::value, st = kt % 3, sn = (kt + 1) % 3;
             uint32_t(&gu)[GA] = (kt % 2 == 0) ? g0 : g1;  // holds step kt + 2's sources
@@ -1298,8 +1061,8 @@ __device__ __forceinline__ void pqg_walk(const p_u32x4 *__restrict__ A, const p_
             issue(IC<(kt + 2) % NK>{}, (kt + 2) % 3, gu);
             if constexpr (kt == 8) issue_map(nxt.m0, cb ^ 1);
             __builtin_amdgcn_sched_barrier(0);
-            half(f0, f1, (uint32_t)st * STG_B, IC<1>{}, IC<1>{});
-            touch(f1);
+            c.half(f0, f1, (uint32_t)st * STG_B, IC<1>{}, IC<1>{});
+            P::touch(f1);
             // step kt + 1 landed; what was issued behind it may stay in flight: the step just issued, at steps 8
             // and 9 the row map's DMAs too, and behind a tile's first step the stores of the tile before it
             if constexpr (kt == 0) {
@@ -1312,12 +1075,12 @@ __device__ __forceinline__ void pqg_walk(const p_u32x4 *__restrict__ A, const p_
             } else {
                 P_VMCNT(G);
             }
-            publish();
+            P::publish();
             read_g((kt + 3) % NK, gn, kt + 3 < NK ? cb : cb ^ 1);
             if constexpr (kt + 1 < NK)
-                half(f1, f0, (uint32_t)sn * STG_B, IC<0>{}, IC<1>{});
+                c.half(f1, f0, (uint32_t)sn * STG_B, IC<0>{}, IC<1>{});
             else
-                half(f1, f0, 0u, IC<0>{}, IC<0>{});
+                c.half(f1, f0, 0u, IC<0>{}, IC<0>{});
         });
         if (cur.t != lt || cur.n0 != ln) load_consts();
         carried = cur.m0 + BM <= M;
@@ -1327,7 +1090,7 @@ __device__ __forceinline__ void pqg_walk(const p_u32x4 *__restrict__ A, const p_
             store_tile(IC<0>{});
             P_VMCNT(0);
         }
-        zero();
+        c.zero();
         if (!more) break;
         v += nb;
         cur = nxt;
@@ -1387,31 +1150,43 @@ int walk_blocks(int64_t items) {
     return n <= 0 ? -1 : (int)std::min<int64_t>(n, items);
 }
 
+// the tiles of an M x N output over T towers and the grid that covers them: (tiles, T) blocks, one per tile, or a
+// walk's blocks
+struct PGrid {
+    int tiles_n, tiles, W;  // column tiles; row x column tiles of one tower; items (tiles of every tower)
+    dim3 grid;
+};
+hipError_t pq_grid(int64_t M, int N, int T, int BM, int BN, bool walk, PGrid &g) {
+    const int64_t tiles_m = (M + BM - 1) / BM;
+    g.tiles_n = N / BN;
+    if (tiles_m * g.tiles_n * T > INT32_MAX) return hipErrorInvalidValue;
+    g.tiles = (int)(tiles_m * g.tiles_n), g.W = g.tiles * T;
+    g.grid = dim3((unsigned)g.tiles, T);
+    if (walk) {
+        const int nb = walk_blocks(g.W);
+        if (nb < 1) return hipErrorInvalidValue;
+        g.grid = dim3(nb);
+    }
+    return hipSuccess;
+}
+
 template <int BM, int BN, int WGM, int WGN, int NS = 3, bool ONE = false, int ORD = 0, bool PERS = false>
 hipError_t pq_launch(const void *A, const void *B, const uint32_t *amaxA, const uint32_t *amaxB, int64_t M, int N,
                      int K, int T, int64_t sA, int64_t sB, const float *bias, float *C, int64_t sC, hipStream_t s) {
     if (N % BN || K % 32 || K < 64) return hipErrorInvalidValue;
-    const int64_t tiles_m = (M + BM - 1) / BM;
-    const int tiles_n = N / BN;
-    if (tiles_m * tiles_n * T > INT32_MAX) return hipErrorInvalidValue;
-    const int tiles = (int)(tiles_m * tiles_n), W = tiles * T;
-    dim3 grid((unsigned)tiles, T);
+    PGrid g;
+    if (pq_grid(M, N, T, BM, BN, PERS, g) != hipSuccess) return hipErrorInvalidValue;
     const dim3 block(64 * WGM * WGN);
-    if constexpr (PERS) {
-        const int nb = walk_blocks(W);
-        if (nb < 1) return hipErrorInvalidValue;
-        grid = dim3(nb);
-    }
     const auto *a = static_cast<const p_u32x4 *>(A);
     const auto *b = static_cast<const p_u32x4 *>(B);
 #define PQ_K(NK)                                                                                                    \
     do {                                                                                                            \
         if (bias)                                                                                                   \
-            hipLaunchKernelGGL((k_h3_pq<BM, BN, WGM, WGN, 1, NK, NS, ONE, ORD, PERS>), grid, block, 0, s, a, b, amaxA, \
-                               amaxB, M, N, K, sA / 4, sB / 4, bias, C, sC, tiles_n, tiles, W);                     \
+            hipLaunchKernelGGL((k_h3_pq<BM, BN, WGM, WGN, 1, NK, NS, ONE, ORD, PERS>), g.grid, block, 0, s, a, b,   \
+                               amaxA, amaxB, M, N, K, sA / 4, sB / 4, bias, C, sC, g.tiles_n, g.tiles, g.W);        \
         else                                                                                                        \
-            hipLaunchKernelGGL((k_h3_pq<BM, BN, WGM, WGN, 0, NK, NS, ONE, ORD, PERS>), grid, block, 0, s, a, b, amaxA, \
-                               amaxB, M, N, K, sA / 4, sB / 4, nullptr, C, sC, tiles_n, tiles, W);                  \
+            hipLaunchKernelGGL((k_h3_pq<BM, BN, WGM, WGN, 0, NK, NS, ONE, ORD, PERS>), g.grid, block, 0, s, a, b,   \
+                               amaxA, amaxB, M, N, K, sA / 4, sB / 4, nullptr, C, sC, g.tiles_n, g.tiles, g.W);     \
     } while (0)
     switch (K) {  // the k loop is unrolled: one instantiation per depth (fc1's forward K = 576, input gradient 512)
         case 576: PQ_K(18); break;
@@ -1443,21 +1218,17 @@ hipError_t launch_h3p_gemm_nt(const void *A, const uint32_t *amaxA, const void *
         constexpr int BM = 128, BN = 256;
         if ((cfg != 60 && cfg != 75 && cfg != 76) || K != 576 || N % BN || !bias || !C) return hipErrorInvalidValue;
         if (head_part && (T != 2 || n_actions < 1 || n_actions > 4 || !head_w0 || !head_w1)) return hipErrorInvalidValue;
-        const int64_t tiles_m = (M + BM - 1) / BM;
-        const int tiles_n = N / BN;
-        if (tiles_m * tiles_n * T > INT32_MAX) return hipErrorInvalidValue;
-        const int tiles = (int)(tiles_m * tiles_n), W = tiles * T;
         const bool walk = cfg == 76 || (cfg == 60 && H3P_FWD_WALK);
         // the walk's DMA sources are 32-bit byte offsets from uniform bases: a tower of A, B's tile rows, the row map
         if (walk && (a_stride > (INT64_C(1) << 30) || M * 9 > (INT64_C(1) << 30))) return hipErrorInvalidValue;
-        const int nb = walk ? walk_blocks(W) : 0;
-        if (walk && nb < 1) return hipErrorInvalidValue;
-        const dim3 grid = walk ? dim3(nb) : dim3((unsigned)tiles, T), block(512);
+        PGrid g;
+        if (pq_grid(M, N, T, BM, BN, walk, g) != hipSuccess) return hipErrorInvalidValue;
+        const dim3 block(512);
         const auto *a = static_cast<const p_u32x4 *>(A);
         const auto *b = static_cast<const p_u32x4 *>(B);
 #define PQG(EPI, PERS, ...)                                                                                          \
-    hipLaunchKernelGGL((k_h3_pqg<BM, BN, 2, 4, EPI, PERS>), grid, block, 0, s, a, b, amaxA, amaxB, M, N, a_stride / 4, \
-                       b_stride / 4, bias, C, c_stride, tiles_n, tiles, W, a_rows, __VA_ARGS__)
+    hipLaunchKernelGGL((k_h3_pqg<BM, BN, 2, 4, EPI, PERS>), g.grid, block, 0, s, a, b, amaxA, amaxB, M, N,           \
+                       a_stride / 4, b_stride / 4, bias, C, c_stride, g.tiles_n, g.tiles, g.W, a_rows, __VA_ARGS__)
         if (head_part && walk)
             PQG(2, true, head_w0, head_w1, n_actions, head_part);
         else if (head_part)
@@ -1469,26 +1240,27 @@ hipError_t launch_h3p_gemm_nt(const void *A, const uint32_t *amaxA, const void *
 #undef PQG
         return hipGetLastError();
     }
-    switch (cfg) {
-        case 60: return pq_launch<128, 256, 2, 4>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
+#define PQ(...) return pq_launch<__VA_ARGS__>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s)
+    switch (cfg) {  // PQ returns; its arguments: <BM, BN, WGM, WGN, NS = 3, ONE = false, ORD = 0, PERS = false>
+        case 60: PQ(128, 256, 2, 4);
         case 62:
-            if (H3P_DGRAD_WALK)
-                return pq_launch<128, 192, 4, 2, 3, false, 0, true>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
-            return pq_launch<128, 192, 4, 2>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
-        case 77: return pq_launch<128, 192, 4, 2>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
-        case 78: return pq_launch<128, 192, 4, 2, 3, false, 0, true>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
+            if (H3P_DGRAD_WALK) PQ(128, 192, 4, 2, 3, false, 0, true);
+            PQ(128, 192, 4, 2);
+        case 77: PQ(128, 192, 4, 2);
+        case 78: PQ(128, 192, 4, 2, 3, false, 0, true);
         // round 6: the same with a 4-stage ring (160 KB of LDS, three k steps in flight)
-        case 63: return pq_launch<128, 192, 4, 2, 4>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
-        // round 6: one accumulator per tile (ONE): 65: 256 x 192 tiles on a 2-stage ring (112 KB), 66: 62's 128 x 192
-        // tile, 68: 256 x 256 over 4 waves (one per SIMD: 512 registers each; 8 waves spill), 69: 192 x 192 over 6
-        // waves, 3 stages (144 KB)
-        case 65: return pq_launch<256, 192, 4, 2, 2, true>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
-        // 66: 62 with the MFMAs product-major (ORD 1: no two consecutive MFMAs on one accumulator; the same bits)
-        case 66: return pq_launch<128, 192, 4, 2, 3, false, 1>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
-        case 68: return pq_launch<256, 256, 2, 2, 2, true>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
-        case 69: return pq_launch<192, 192, 3, 2, 3, true>(A, B, amaxA, amaxB, M, N, K, T, a_stride, b_stride, bias, C, c_stride, s);
+        case 63: PQ(128, 192, 4, 2, 4);
+        // round 6: one accumulator per tile (ONE): 65: 256 x 192 tiles on a 2-stage ring (112 KB), 68: 256 x 256 over
+        // 4 waves (one per SIMD: 512 registers each; 8 waves spill), 69: 192 x 192 over 6 waves, 3 stages (144 KB)
+        case 65: PQ(256, 192, 4, 2, 2, true);
+        // 66: 62's one-tile form with the MFMAs product-major (ORD 1: no two consecutive MFMAs on one accumulator;
+        // the same bits)
+        case 66: PQ(128, 192, 4, 2, 3, false, 1);
+        case 68: PQ(256, 256, 2, 2, 2, true);
+        case 69: PQ(192, 192, 3, 2, 3, true);
         default: return hipErrorInvalidValue;
     }
+#undef PQ
 }
 
 

@@ -450,7 +450,7 @@ __device__ __forceinline__ void block_amax2(const uint32_t mx[2], int T, uint32_
 // The h3 operand form (merlin_h3.hip's header comment): per tower one power-of-two scale 2^e from a bound on max |x|,
 // per value an f16 hi plane and an f16 lo plane (x 2^11).  Shared by merlin_h3.hip's splits and the producers that
 // write their output as planes directly (k_head_bwd's dz, conv3's representatives).
-constexpr float H3_LO_SCALE = 2048.0f;
+constexpr float H3_LO_SCALE = 2048.0f, H3_LO_INV = 1.0f / H3_LO_SCALE;
 // the scale exponent e of a tensor whose max |x| (or a bound on it) has float bits `amax`: amax 2^e in [2^14, 2^15)
 __device__ __forceinline__ int h3_exp(uint32_t amax) {
     if (amax == 0u) return 0;
@@ -458,6 +458,16 @@ __device__ __forceinline__ int h3_exp(uint32_t amax) {
     return min(max(14 - e, -120), 115);                // e + 11 stays a normal power of two
 }
 __device__ __forceinline__ float pow2f(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
+// an operand scale written by another kernel's atomics: read with a vector load at agent scope (L2-coherent), not
+// through the scalar data cache a wave-uniform load would take
+__device__ __forceinline__ uint32_t load_amax(const uint32_t *p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// block b of nb -> its tile, so that the blocks of one XCD (b % 8) work on consecutive tiles
+__device__ __forceinline__ int xcd_tile(int b, int nb) {
+    const int xcd = b & 7, q = nb >> 3, r = nb & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
+}
 
 // planes of two unscaled values a, b (sc = 2^e, sc2 = 2^(e + 11)): hi word (h of a, h of b) = f16(x'), lo word =
 // f16(2^11 x' - 2^11 h), each by one v_fma_mix{lo,hi}_f16 (the mixed fma rounds its exact result once to f16; in
