@@ -20,30 +20,25 @@
 //
 // Scales: merlin_h3_amax writes max |x| per tower as float bits (uint32, atomicMax of non-negative floats); the
 // GEMMs read it and derive e in-kernel, so no host round trip.
+//
+// Shared with merlin_h3p.hip through merlin_h3_tile.h: the vector types, mfma16, g_swz, the accumulator tile H3Tile
+// (zero, the three-MFMA tile product, the plain and heads epilogues) and the TN bodies' transposed fragment read.
+// The TN side is one body, h3_tn_body, on that tile.  The three NT bodies (k_h3_nt, h3_ntp_body, k_h3_ntg) still
+// hold their accumulators and epilogues themselves: moved onto H3Tile, 20 of their instantiations were allocated
+// more VGPRs (k_h3_ntp<64, 128, 2, 2, 0 / 1> 164 -> 172, across the three-waves-per-SIMD line; the rollout's
+// heads-only k_h3_ntp<128, 128, 2, 2, 3> 284 -> 300), profiles/r10_isa_compare.md.
 #include <algorithm>
 
+#include "merlin_h3_tile.h"
 #include "merlin_internal.h"
 
 namespace merlin {
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-typedef __attribute__((address_space(3))) char lds_char;
-
 constexpr int BK = 32;           // k per step
 constexpr float LO_INV = H3_LO_INV;
 
-__device__ __forceinline__ f32x16 mfma16(const u32x4 a, const u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0,
-                                                   0);
-}
-
+// the vector types, mfma16, the accumulator tile H3Tile and the TN fragment read: merlin_h3_tile.h
 // relu_nan / xcd_tile / h3_exp / pow2f / load_amax / h3_pair: merlin_internal.h (shared with merlin_h3p.hip and the
 // producers that write planes)
 
@@ -561,7 +556,6 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_ntpg(const float *__restr
 // lane-linear, so the permutation is applied to the global source address; a fragment read (16 lanes of a
 // ds_read_b128 group, 16 different rows, one chunk) then hits 16 distinct 16-B bank slots.  Raw s_barrier with
 // counted vmcnt: the DMA of step kt + 2 stays in flight across the barrier that publishes step kt + 1.
-__device__ __forceinline__ int g_swz(int r) { return (r >> 1) & 7; }
 
 template <int BM, int BN, int WGM, int WGN, int EPI, bool KP>
 __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_ntg(const float *__restrict__ A, const u32x4 *__restrict__ B,
@@ -771,53 +765,44 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_ntg(const float *__restri
 // ---------------------------------------------------------------------------------------------------------------
 // TN: slab[s][t][m][n] = sum_{k in split s} A[t][k][m] B[t][k][n], A fp32 [Kd][M], B fp32 [Kd][N] (the weight
 // gradient dz^T a3: both operands row-major over the minibatch's frames), both split while staged into plane
-// images [32 k rows][RC chunks of 8 columns]; fragments k-contiguous through ds_read_b64_tr_b16 (a 32x32x16
-// fragment, lane l: column l & 31, k = 8 (l >> 5) + j, is two transposed reads: 16-lane group g takes columns
-// 16 (g & 1) .. + 15 and k rows 8 (g >> 1) + 4 h2 .. + 3).  Chunk c of row r sits at r RC + (c ^ swz(r)): the 16
-// chunks a 32-lane half reads (4 rows x 4 adjacent chunks) land on 16 distinct 16-B bank slots for RC = 16 (XOR
-// 4 (r & 3)) and RC = 24 (XOR 4 ((r >> 1) & 1)).  Slabs are written already unscaled (x 2^-(eA + eB), exact).
-template <int RC>
-__device__ __forceinline__ int tr_swz(int row) {
-    // RC = 8 (128-B rows) as RC = 24: two rows per 256-B bank row, rows r and r + 2 on the same slots
-    static_assert(RC % 16 == 0 || RC == 24 || RC == 8, "row chunks");
-    return RC % 16 == 0 ? (row & 3) << 2 : ((row >> 1) & 1) << 2;
-}
-
-template <int RC>
-__device__ __forceinline__ u32x4 tr_frag(const u32x4 *img, int col0, int kh, int lane) {
-    const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-    const int chunk = ((col0 + 16 * (g & 1)) >> 3) + (p >> 1);
-    bf16x4 v[2];  // 16-bit lanes moved as bits (the planes are f16)
-#pragma unroll
-    for (int h2 = 0; h2 < 2; h2++) {
-        const int row = 16 * kh + 8 * (g >> 1) + 4 * h2 + q;
-        const int off = (row * RC + (chunk ^ tr_swz<RC>(row))) * 16 + (p & 1) * 8;
-        v[h2] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4 *)((lds_char *)img + off));
-    }
-    return __builtin_bit_cast(u32x4, bf16x8{v[0][0], v[0][1], v[0][2], v[0][3], v[1][0], v[1][1], v[1][2], v[1][3]});
-}
-
+// images [32 k rows][RC chunks of 8 columns], fragments k-contiguous through transposed reads (the images and
+// tr_frag: merlin_h3_tile.h).  Slabs are written already unscaled (x 2^-(eA + eB), exact).  Two LDS stages, one
+// barrier per k step, the step after next in registers, as k_h3_nt.  One body, h3_tn_body, for the four kernels
+// below; what differs between them is compile-time:
 // GB: B's rows gathered by 64-column chunks -- row k's chunk j is row bmap[k * N / 64 + j] of B seen as [*][64] (the
 // minibatch's conv3 rows through their patch representatives, as k_h3_ntp's GA).  A unit's chunk is fixed, its row
 // changes every k step: each load issues the next step's chunk-row reads behind its data reads (ready by then).
 // AQ: A arrives as plane images ([Kd][M/8][2][8] f16, 4 B per value like fp32, so the addressing is the same): its
 // staging copies the hi / lo chunks instead of splitting (k_head_bwd's dz planes, merlin_tower_head_bwd_planes)
 // BQ: B (gathered) arrives as plane images too (conv3's representatives as planes)
-template <int BM, int BN, int WGM, int WGN, bool GB, bool AQ = false, bool BQ = false>
+// QC (k_h3_tnq): both operands are plane images ([T][Kd][cols/8][2][8] f16 -- the a_planes output of the NT kernels,
+// so the fast step's weight gradient reads the planes its forward and input-gradient GEMMs made) and a staging unit
+// is one 16-B chunk of one plane, not a (k row, 8 columns) pair of them: thread q of a k row takes plane q / RC,
+// chunk q % RC, so the 8 lanes of a ds_write_b128 group write 8 chunks of one plane image (8 distinct bank slots).
+// PIPE (k_h3_tnp): the k step's split and staging interleaved into its MFMAs, as k_h3_ntp does for NT: the steps
+// whose loads are whole (all but a split's last one or two) run in a loop with no conditional part, each reading its
+// fragments first, then sched_group_barrier hints lay the next step's split (VALU), its LDS stores and the global
+// loads of the step after it between the MFMAs; the remaining steps run as without PIPE.  Same instructions per
+// output, the same order of products and sums: the same bits.
+template <int BM, int BN, int WGM, int WGN, bool GB, bool AQ = false, bool BQ = false, bool QC = false,
+          bool PIPE = false>
 __device__ __forceinline__ void h3_tn_body(const float4 *__restrict__ A, const float4 *__restrict__ B,
                                            const uint32_t *__restrict__ amaxA, const uint32_t *__restrict__ amaxB,
                                            int64_t Kd, int M, int N, int64_t sA, int64_t sB, int64_t kc, int tiles_n,
                                            int tiles, int S, float *__restrict__ slab,
                                            const int32_t *__restrict__ bmap) {
-    constexpr int NT = 64 * WGM * WGN;
-    constexpr int WTM = BM / WGM, WTN = BN / WGN;
-    constexpr int TM = WTM / 32, TN = WTN / 32;
+    using TL = H3Tile<BM, BN, WGM, WGN>;
+    constexpr int NT = TL::NT, WTM = TL::WTM, WTN = TL::WTN, TM = TL::TM, TN = TL::TN;
     constexpr int RCA = BM / 8, RCB = BN / 8;
-    constexpr int QA = BK * RCA, QB = BK * RCB;  // units (k row, group of 8 columns) per k step
+    constexpr int NP = QC ? 2 : 1, NV = 2 / NP;        // planes a k row's units are spread over; 16-B loads per unit
+    constexpr int QA = BK * RCA * NP, QB = BK * RCB * NP;  // units per k step
     constexpr int UA = (QA + NT - 1) / NT, UB = (QB + NT - 1) / NT;
-    static_assert(WTM % 32 == 0 && WTN % 32 == 0, "wave tile of 32 x 32 MFMA tiles");
+    static_assert(!QC || (!GB && QA % NT == 0 && QB % NT == 0 && RCA % 8 == 0 && RCB % 8 == 0),
+                  "whole staging chunks per thread");
+    static_assert(!PIPE || (!GB && !QC), "the scheduled loop: fp32 operands, no gather");
     constexpr int PSA = BK * RCA, PSB = BK * RCB;
     constexpr int STAGE = 2 * (PSA + PSB);
+    constexpr int NMFMA = TM * TN * 6;  // per k step and wave
     __shared__ u32x4 lds[2 * STAGE];
 
     // 1-D grid over (tower, split, tile), tile fastest, XCD-contiguous: the tiles of one split read the same k rows
@@ -828,12 +813,13 @@ __device__ __forceinline__ void h3_tn_body(const float4 *__restrict__ A, const f
     const int64_t k0 = (int64_t)s * kc, k1 = std::min<int64_t>(Kd, k0 + kc);
     const int eA = h3_exp(load_amax(amaxA + t)), eB = h3_exp(load_amax(amaxB + t));
     const float scA = pow2f(eA), scB = pow2f(eB), scA2 = pow2f(eA + 11), scB2 = pow2f(eB + 11);
-    const int64_t rowA = M / 4, rowB = N / 4;
+    const int64_t rowA = M / 4, rowB = N / 4;  // 16-B chunks per k row
     A += t * sA + m0 / 4;
     B += t * sB + (GB ? 0 : n0 / 4);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int wm = w / WGN, wn = w - (w / WGN) * WGN;
 
+    // unit q of an operand: k row, plane p (QC; else both) and column group g -> image slot l, source pointer
     int ka[UA], la[UA], kb[UB], lb[UB];
     const float4 *pa[UA], *pb[UB];
     constexpr bool PAIR = GB && 8 % UB == 0 && RCB % UB == 0;
@@ -843,25 +829,25 @@ __device__ __forceinline__ void h3_tn_body(const float4 *__restrict__ A, const f
 #pragma unroll
     for (int i = 0; i < UA; i++) {
         const int q = std::min(tid + i * NT, QA - 1);
-        const int k = q / RCA, g = q - (q / RCA) * RCA;
+        const int k = q / (NP * RCA), c = q - k * (NP * RCA), p = QC ? c / RCA : 0, g = c - p * RCA;
         ka[i] = k;
-        la[i] = k * RCA + (g ^ tr_swz<RCA>(k));
-        pa[i] = A + (k0 + k) * rowA + g * 2;
+        la[i] = p * PSA + k * RCA + (g ^ tr_swz<RCA>(k));
+        pa[i] = A + (k0 + k) * rowA + g * 2 + p;
     }
 #pragma unroll
     for (int i = 0; i < UB; i++) {
         // GB with PAIR: a thread's UB units are adjacent column groups of one row and one 64-column chunk, so they
         // share one chunk row (one index read per thread and step)
         const int q = std::min(PAIR ? UB * tid + i : tid + i * NT, QB - 1);
-        const int k = q / RCB, g = q - (q / RCB) * RCB;
+        const int k = q / (NP * RCB), c = q - k * (NP * RCB), p = QC ? c / RCB : 0, g = c - p * RCB;
         kb[i] = k;
-        lb[i] = 2 * PSA + k * RCB + (g ^ tr_swz<RCB>(k));
+        lb[i] = 2 * PSA + p * PSB + k * RCB + (g ^ tr_swz<RCB>(k));
         if constexpr (GB) {
             const int col = n0 + 8 * g;
             pb[i] = B + (col & 63) / 4;
             mb[i] = bmap + (k0 + k) * nc + (col >> 6);
         } else {
-            pb[i] = B + (k0 + k) * rowB + g * 2;
+            pb[i] = B + (k0 + k) * rowB + g * 2 + p;
         }
     }
     auto fetch_rows = [&](int64_t kk) {  // GB: chunk rows of step kk (rows past k1 clamped, zeroed when staged)
@@ -880,24 +866,30 @@ __device__ __forceinline__ void h3_tn_body(const float4 *__restrict__ A, const f
         }
     };
     const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    float4 ra[UA][2], rb[UB][2];
+    float4 ra[UA][2], rb[UB][2];  // (QC: [0] only)
+    // an operand's units of step kk into registers.  WHOLE (kk + BK <= k1): row pointers + a wave-uniform offset; a
+    // split's last step otherwise: rows past k1 re-read row k1 - 1, zeroed when staged
+    auto rows = [&](auto &r, const auto &ptr, const auto &kq, int64_t row, int64_t kk, auto WHOLE) {
+#pragma unroll
+        for (int i = 0; i < (int)(sizeof(r) / sizeof(r[0])); i++) {
+            const float4 *src =
+                ptr[i] + (decltype(WHOLE)::value ? kk - k0 : std::min(kk + kq[i], k1 - 1) - k0 - kq[i]) * row;
+#pragma unroll
+            for (int v = 0; v < NV; v++) r[i][v] = src[v];
+        }
+    };
+    auto load_whole = [&](int64_t kk) {
+        rows(ra, pa, ka, rowA, kk, IC<1>{});
+        if constexpr (!GB) rows(rb, pb, kb, rowB, kk, IC<1>{});
+    };
     auto load = [&](int64_t kk) {
+        if (kk + BK <= k1) {
+            load_whole(kk);
+        } else {
+            rows(ra, pa, ka, rowA, kk, IC<0>{});
+            if constexpr (!GB) rows(rb, pb, kb, rowB, kk, IC<0>{});
+        }
         if constexpr (GB) {
-            if (kk + BK <= k1) {
-                const int64_t da = (kk - k0) * rowA;
-#pragma unroll
-                for (int i = 0; i < UA; i++) {
-                    ra[i][0] = pa[i][da];
-                    ra[i][1] = pa[i][da + 1];
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < UA; i++) {
-                    const float4 *src = pa[i] + (std::min(kk + ka[i], k1 - 1) - k0 - ka[i]) * rowA;
-                    ra[i][0] = src[0];
-                    ra[i][1] = src[1];
-                }
-            }
 #pragma unroll
             for (int i = 0; i < UB; i++) {
                 const float4 *src = pb[i] + (int64_t)xb[i] * 16;
@@ -905,485 +897,147 @@ __device__ __forceinline__ void h3_tn_body(const float4 *__restrict__ A, const f
                 rb[i][1] = src[1];
             }
             fetch_rows(kk + BK);
-            return;
         }
-        if (kk + BK <= k1) {  // full step: row pointers + a wave-uniform offset
-            const int64_t da = (kk - k0) * rowA, db = (kk - k0) * rowB;
-#pragma unroll
-            for (int i = 0; i < UA; i++) {
-                ra[i][0] = pa[i][da];
-                ra[i][1] = pa[i][da + 1];
-            }
-#pragma unroll
-            for (int i = 0; i < UB; i++) {
-                rb[i][0] = pb[i][db];
-                rb[i][1] = pb[i][db + 1];
-            }
-            return;
-        }
-#pragma unroll
-        for (int i = 0; i < UA; i++) {  // a split's last step: rows past k1 re-read row k1 - 1, zeroed when staged
-            const float4 *src = pa[i] + (std::min(kk + ka[i], k1 - 1) - k0 - ka[i]) * rowA;
-            ra[i][0] = src[0];
-            ra[i][1] = src[1];
-        }
-#pragma unroll
-        for (int i = 0; i < UB; i++) {
-            const float4 *src = pb[i] + (std::min(kk + kb[i], k1 - 1) - k0 - kb[i]) * rowB;
-            rb[i][0] = src[0];
-            rb[i][1] = src[1];
+    };
+    // a unit's registers into its image slot (in: its k row is inside the split, else zeros).  QC: one plane's chunk;
+    // otherwise both planes, PL: copied (the operand is plane images), else split at scale sc (sc2 = 2^11 sc)
+    auto put = [&](u32x4 *st, int l, int PS, const float4 (&r)[2], bool in, auto PL, float sc, float sc2) {
+        u32x4 p0 = __builtin_bit_cast(u32x4, in ? r[0] : zero), p1;
+        if constexpr (QC) {
+            st[l] = p0;
+        } else {
+            if constexpr (decltype(PL)::value)
+                p1 = __builtin_bit_cast(u32x4, in ? r[1] : zero);
+            else
+                h3_split8(in ? r[0] : zero, in ? r[1] : zero, sc, sc2, p0, p1);
+            st[l] = p0;
+            st[PS + l] = p1;
         }
     };
     auto store = [&](int buf, int64_t kk) {
         u32x4 *st = lds + buf * STAGE;
 #pragma unroll
         for (int i = 0; i < UA; i++)
-            if (QA % NT == 0 || i + 1 < UA || tid + i * NT < QA) {
-                const bool in = kk + ka[i] < k1;
-                u32x4 p0, p1;
-                if constexpr (AQ) {
-                    p0 = __builtin_bit_cast(u32x4, in ? ra[i][0] : zero);
-                    p1 = __builtin_bit_cast(u32x4, in ? ra[i][1] : zero);
-                } else {
-                    h3_split8(in ? ra[i][0] : zero, in ? ra[i][1] : zero, scA, scA2, p0, p1);
-                }
-                st[la[i]] = p0;
-                st[PSA + la[i]] = p1;
-            }
+            if (QA % NT == 0 || i + 1 < UA || tid + i * NT < QA)
+                put(st, la[i], PSA, ra[i], kk + ka[i] < k1, IC<AQ>{}, scA, scA2);
 #pragma unroll
         for (int i = 0; i < UB; i++)
-            if (PAIR ? UB * tid + i < QB : (QB % NT == 0 || i + 1 < UB || tid + i * NT < QB)) {
-                const bool in = kk + kb[i] < k1;
-                u32x4 p0, p1;
-                if constexpr (BQ) {
-                    p0 = __builtin_bit_cast(u32x4, in ? rb[i][0] : zero);
-                    p1 = __builtin_bit_cast(u32x4, in ? rb[i][1] : zero);
-                } else {
-                    h3_split8(in ? rb[i][0] : zero, in ? rb[i][1] : zero, scB, scB2, p0, p1);
-                }
-                st[lb[i]] = p0;
-                st[PSB + lb[i]] = p1;
-            }
+            if (PAIR ? UB * tid + i < QB : (QB % NT == 0 || i + 1 < UB || tid + i * NT < QB))
+                put(st, lb[i], PSB, rb[i], kk + kb[i] < k1, IC<BQ>{}, scB, scB2);
     };
 
-    f32x16 hi[TM][TN], lo[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-        for (int j = 0; j < TN; j++) {
-            hi[i][j] = f32x16{};
-            lo[i][j] = f32x16{};
-        }
-
-    if (k0 < k1) {
-        fetch_rows(k0);
-        load(k0);
-        store(0, k0);
-        if (k0 + BK < k1) load(k0 + BK);
-        __syncthreads();
-    }
-    int buf = 0;
-    for (int64_t kk = k0; kk < k1; kk += BK, buf ^= 1) {
-        if (kk + BK < k1) store(buf ^ 1, kk + BK);
-        if (kk + 2 * BK < k1) load(kk + 2 * BK);
-        const u32x4 *sAl = lds + buf * STAGE, *sBl = sAl + 2 * PSA;
-        u32x4 af[TM][2][2];
-#pragma unroll
-        for (int i = 0; i < TM; i++)
-#pragma unroll
-            for (int kh = 0; kh < 2; kh++)
-#pragma unroll
-                for (int p = 0; p < 2; p++) af[i][kh][p] = tr_frag<RCA>(sAl + p * PSA, wm * WTM + i * 32, kh, lane);
-#pragma unroll
-        for (int j = 0; j < TN; j++) {
-            u32x4 bf[2][2];
-#pragma unroll
-            for (int kh = 0; kh < 2; kh++)
-#pragma unroll
-                for (int p = 0; p < 2; p++) bf[kh][p] = tr_frag<RCB>(sBl + p * PSB, wn * WTN + j * 32, kh, lane);
-#pragma unroll
-            for (int i = 0; i < TM; i++) {
-                f32x16 l = lo[i][j], h = hi[i][j];
-#pragma unroll
-                for (int kh = 0; kh < 2; kh++) {
-                    l = mfma16(af[i][kh][1], bf[kh][0], l);
-                    l = mfma16(af[i][kh][0], bf[kh][1], l);
-                    h = mfma16(af[i][kh][0], bf[kh][0], h);
-                }
-                lo[i][j] = l;
-                hi[i][j] = h;
-            }
-        }
-        __syncthreads();
-    }
-
-    const float inv = pow2f(-eA), invB = pow2f(-eB);
-    float *St = slab + ((int64_t)s * (gridDim.x / (S * tiles)) + t) * (int64_t)M * N;
-    const int fr = lane & 31, fh = lane >> 5;
-#pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-        for (int j = 0; j < TN; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int row = m0 + wm * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                St[(int64_t)row * N + n0 + wn * WTN + j * 32 + fr] =
-                    (hi[i][j][r] + lo[i][j][r] * LO_INV) * inv * invB;
-            }
-}
-
-template <int BM, int BN, int WGM, int WGN>
-__global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tn(const float4 *__restrict__ A, const float4 *__restrict__ B,
-                                                          const uint32_t *__restrict__ amaxA,
-                                                          const uint32_t *__restrict__ amaxB, int64_t Kd, int M, int N,
-                                                          int64_t sA, int64_t sB, int64_t kc, int tiles_n, int tiles,
-                                                          int S, float *__restrict__ slab) {
-    h3_tn_body<BM, BN, WGM, WGN, false>(A, B, amaxA, amaxB, Kd, M, N, sA, sB, kc, tiles_n, tiles, S, slab, nullptr);
-}
-template <int BM, int BN, int WGM, int WGN, bool AQ = false, bool BQ = false>
-__global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tng(const float4 *__restrict__ A, const float4 *__restrict__ B,
-                                                           const uint32_t *__restrict__ amaxA,
-                                                           const uint32_t *__restrict__ amaxB, int64_t Kd, int M,
-                                                           int N, int64_t sA, int64_t sB, int64_t kc, int tiles_n,
-                                                           int tiles, int S, float *__restrict__ slab,
-                                                           const int32_t *__restrict__ bmap) {
-    h3_tn_body<BM, BN, WGM, WGN, true, AQ, BQ>(A, B, amaxA, amaxB, Kd, M, N, sA, sB, kc, tiles_n, tiles, S, slab,
-                                               bmap);
-}
-
-// The TN product with the k step's split and staging interleaved into its MFMAs, as k_h3_ntp does for NT: the
-// steps whose loads are whole (all but a split's last one or two) run in a loop with no conditional part, each
-// reading its fragments first, then sched_group_barrier hints lay the next step's split (VALU), its LDS stores and
-// the global loads of the step after it between the MFMAs; the remaining steps run as in k_h3_tn.  Same
-// instructions per output as k_h3_tn, the same order of products and sums: the same bits.
-template <int BM, int BN, int WGM, int WGN>
-__global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tnp(const float4 *__restrict__ A, const float4 *__restrict__ B,
-                                                           const uint32_t *__restrict__ amaxA,
-                                                           const uint32_t *__restrict__ amaxB, int64_t Kd, int M,
-                                                           int N, int64_t sA, int64_t sB, int64_t kc, int tiles_n,
-                                                           int tiles, int S, float *__restrict__ slab) {
-    constexpr int NT = 64 * WGM * WGN;
-    constexpr int WTM = BM / WGM, WTN = BN / WGN;
-    constexpr int TM = WTM / 32, TN = WTN / 32;
-    constexpr int RCA = BM / 8, RCB = BN / 8;
-    constexpr int QA = BK * RCA, QB = BK * RCB;
-    constexpr int UA = (QA + NT - 1) / NT, UB = (QB + NT - 1) / NT;
-    static_assert(WTM % 32 == 0 && WTN % 32 == 0, "wave tile of 32 x 32 MFMA tiles");
-    constexpr int PSA = BK * RCA, PSB = BK * RCB;
-    constexpr int STAGE = 2 * (PSA + PSB);
-    constexpr int NMFMA = TM * TN * 6;
-    __shared__ u32x4 lds[2 * STAGE];
-
-    const int P = xcd_tile(blockIdx.x, gridDim.x);
-    const int t = P / (S * tiles), s = (P / tiles) % S, Lt = P % tiles;
-    const int tm = Lt / tiles_n, tn = Lt - tm * tiles_n;
-    const int m0 = tm * BM, n0 = tn * BN;
-    const int64_t k0 = (int64_t)s * kc, k1 = std::min<int64_t>(Kd, k0 + kc);
-    const int eA = h3_exp(load_amax(amaxA + t)), eB = h3_exp(load_amax(amaxB + t));
-    const float scA = pow2f(eA), scB = pow2f(eB), scA2 = pow2f(eA + 11), scB2 = pow2f(eB + 11);
-    const int64_t rowA = M / 4, rowB = N / 4;
-    A += t * sA + m0 / 4;
-    B += t * sB + n0 / 4;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wm = w / WGN, wn = w - (w / WGN) * WGN;
-
-    int ka[UA], la[UA], kb[UB], lb[UB];
-    const float4 *pa[UA], *pb[UB];
-#pragma unroll
-    for (int i = 0; i < UA; i++) {
-        const int q = std::min(tid + i * NT, QA - 1);
-        const int k = q / RCA, g = q - (q / RCA) * RCA;
-        ka[i] = k;
-        la[i] = k * RCA + (g ^ tr_swz<RCA>(k));
-        pa[i] = A + (k0 + k) * rowA + g * 2;
-    }
-#pragma unroll
-    for (int i = 0; i < UB; i++) {
-        const int q = std::min(tid + i * NT, QB - 1);
-        const int k = q / RCB, g = q - (q / RCB) * RCB;
-        kb[i] = k;
-        lb[i] = 2 * PSA + k * RCB + (g ^ tr_swz<RCB>(k));
-        pb[i] = B + (k0 + k) * rowB + g * 2;
-    }
-    const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    float4 ra[UA][2], rb[UB][2];
-    auto load_full = [&](int64_t kk) {
-        const int64_t da = (kk - k0) * rowA, db = (kk - k0) * rowB;
-#pragma unroll
-        for (int i = 0; i < UA; i++) {
-            ra[i][0] = pa[i][da];
-            ra[i][1] = pa[i][da + 1];
-        }
-#pragma unroll
-        for (int i = 0; i < UB; i++) {
-            rb[i][0] = pb[i][db];
-            rb[i][1] = pb[i][db + 1];
-        }
-    };
-    auto load = [&](int64_t kk) {
-        if (kk + BK <= k1) {
-            load_full(kk);
-            return;
-        }
-#pragma unroll
-        for (int i = 0; i < UA; i++) {
-            const float4 *src = pa[i] + (std::min(kk + ka[i], k1 - 1) - k0 - ka[i]) * rowA;
-            ra[i][0] = src[0];
-            ra[i][1] = src[1];
-        }
-#pragma unroll
-        for (int i = 0; i < UB; i++) {
-            const float4 *src = pb[i] + (std::min(kk + kb[i], k1 - 1) - k0 - kb[i]) * rowB;
-            rb[i][0] = src[0];
-            rb[i][1] = src[1];
-        }
-    };
-    auto store = [&](int buf, int64_t kk) {
-        u32x4 *st = lds + buf * STAGE;
-#pragma unroll
-        for (int i = 0; i < UA; i++)
-            if (QA % NT == 0 || i + 1 < UA || tid + i * NT < QA) {
-                const bool in = kk + ka[i] < k1;
-                u32x4 p0, p1;
-                h3_split8(in ? ra[i][0] : zero, in ? ra[i][1] : zero, scA, scA2, p0, p1);
-                st[la[i]] = p0;
-                st[PSA + la[i]] = p1;
-            }
-#pragma unroll
-        for (int i = 0; i < UB; i++)
-            if (QB % NT == 0 || i + 1 < UB || tid + i * NT < QB) {
-                const bool in = kk + kb[i] < k1;
-                u32x4 p0, p1;
-                h3_split8(in ? rb[i][0] : zero, in ? rb[i][1] : zero, scB, scB2, p0, p1);
-                st[lb[i]] = p0;
-                st[PSB + lb[i]] = p1;
-            }
-    };
-
-    f32x16 hi[TM][TN], lo[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-        for (int j = 0; j < TN; j++) {
-            hi[i][j] = f32x16{};
-            lo[i][j] = f32x16{};
-        }
+    TL c;
+    c.zero();
+    // a k step's MFMAs, j-major; PIPE reads all its fragments first
     auto compute = [&](int buf) {
         const u32x4 *sAl = lds + buf * STAGE, *sBl = sAl + 2 * PSA;
         u32x4 af[TM][2][2], bf[TN][2][2];
-#pragma unroll
-        for (int i = 0; i < TM; i++)
-#pragma unroll
-            for (int kh = 0; kh < 2; kh++)
-#pragma unroll
-                for (int p = 0; p < 2; p++) af[i][kh][p] = tr_frag<RCA>(sAl + p * PSA, wm * WTM + i * 32, kh, lane);
-#pragma unroll
-        for (int j = 0; j < TN; j++)
+        auto read_b = [&](int j) {
 #pragma unroll
             for (int kh = 0; kh < 2; kh++)
 #pragma unroll
                 for (int p = 0; p < 2; p++) bf[j][kh][p] = tr_frag<RCB>(sBl + p * PSB, wn * WTN + j * 32, kh, lane);
-#pragma unroll
-        for (int j = 0; j < TN; j++)
-#pragma unroll
-            for (int i = 0; i < TM; i++) {
-                f32x16 l = lo[i][j], h = hi[i][j];
-#pragma unroll
-                for (int kh = 0; kh < 2; kh++) {
-                    l = mfma16(af[i][kh][1], bf[j][kh][0], l);
-                    l = mfma16(af[i][kh][0], bf[j][kh][1], l);
-                    h = mfma16(af[i][kh][0], bf[j][kh][0], h);
-                }
-                lo[i][j] = l;
-                hi[i][j] = h;
-            }
-    };
-
-    const int64_t nsteps = k0 < k1 ? (k1 - k0 + BK - 1) / BK : 0, nfull = k0 < k1 ? (k1 - k0) / BK : 0;
-    if (nsteps > 0) {
-        load(k0);
-        store(0, k0);
-        if (nsteps > 1) load(k0 + BK);
-        __syncthreads();
-    }
-    int buf = 0;
-    int64_t st = 0, kk = k0;
-    for (; st + 2 < nfull; st++, kk += BK, buf ^= 1) {  // the load of step st + 2 is whole
-        compute(buf);
-        store(buf ^ 1, kk + BK);
-        load_full(kk + 2 * BK);
-        __builtin_amdgcn_sched_group_barrier(0x100, (TM + TN) * 8, 0);
-#pragma unroll
-        for (int m = 0; m < NMFMA; m++) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-            if (m % 3 == 2) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-            if (m >= NMFMA / 2 && m % 2 == 1) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-        }
-        __syncthreads();
-    }
-    for (; st < nsteps; st++, kk += BK, buf ^= 1) {
-        if (st + 1 < nsteps) store(buf ^ 1, kk + BK);
-        if (st + 2 < nsteps) load(kk + 2 * BK);
-        compute(buf);
-        __syncthreads();
-    }
-
-    const float inv = pow2f(-eA), invB = pow2f(-eB);
-    float *Sl = slab + ((int64_t)s * (gridDim.x / (S * tiles)) + t) * (int64_t)M * N;
-    const int fr = lane & 31, fh = lane >> 5;
-#pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-        for (int j = 0; j < TN; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int row = m0 + wm * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                Sl[(int64_t)row * N + n0 + wn * WTN + j * 32 + fr] =
-                    (hi[i][j][r] + lo[i][j][r] * LO_INV) * inv * invB;
-            }
-}
-
-// TN over operands already in plane form ([T][Kd][cols/8][2][8] f16 -- the a_planes output of the NT kernels, so
-// the fast step's weight gradient reads the planes its forward and input-gradient GEMMs made): k_h3_tn without the
-// split, staging a copy of 16-B chunks.  Thread q of a k row takes plane q / RC, chunk q % RC: the 8 lanes of a
-// ds_write_b128 group write 8 chunks of one plane image (8 distinct bank slots).
-template <int BM, int BN, int WGM, int WGN>
-__global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tnq(const u32x4 *__restrict__ A, const u32x4 *__restrict__ B,
-                                                           const uint32_t *__restrict__ amaxA,
-                                                           const uint32_t *__restrict__ amaxB, int64_t Kd, int M,
-                                                           int N, int64_t sA, int64_t sB, int64_t kc, int tiles_n,
-                                                           int tiles, int S, float *__restrict__ slab) {
-    constexpr int NT = 64 * WGM * WGN;
-    constexpr int WTM = BM / WGM, WTN = BN / WGN;
-    constexpr int TM = WTM / 32, TN = WTN / 32;
-    constexpr int RCA = BM / 8, RCB = BN / 8;
-    constexpr int QA = BK * RCA * 2, QB = BK * RCB * 2;  // chunks per k step
-    constexpr int UA = QA / NT, UB = QB / NT;
-    static_assert(WTM % 32 == 0 && WTN % 32 == 0, "wave tile of 32 x 32 MFMA tiles");
-    static_assert(QA % NT == 0 && QB % NT == 0 && RCA % 8 == 0 && RCB % 8 == 0, "whole staging chunks per thread");
-    constexpr int PSA = BK * RCA, PSB = BK * RCB;
-    constexpr int STAGE = 2 * (PSA + PSB);
-    __shared__ u32x4 lds[2 * STAGE];
-
-    const int P = xcd_tile(blockIdx.x, gridDim.x);
-    const int t = P / (S * tiles), s = (P / tiles) % S, Lt = P % tiles;
-    const int tm = Lt / tiles_n, tn = Lt - tm * tiles_n;
-    const int m0 = tm * BM, n0 = tn * BN;
-    const int64_t k0 = (int64_t)s * kc, k1 = std::min<int64_t>(Kd, k0 + kc);
-    const int eA = h3_exp(load_amax(amaxA + t)), eB = h3_exp(load_amax(amaxB + t));
-    const int64_t rowA = M / 4, rowB = N / 4;  // chunks per k row
-    A += t * sA + m0 / 4;
-    B += t * sB + n0 / 4;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wm = w / WGN, wn = w - (w / WGN) * WGN;
-
-    int ka[UA], la[UA], kb[UB], lb[UB];
-    const u32x4 *pa[UA], *pb[UB];
-#pragma unroll
-    for (int i = 0; i < UA; i++) {
-        const int q = tid + i * NT;
-        const int k = q / (2 * RCA), c = q - k * (2 * RCA), p = c / RCA, g = c - p * RCA;
-        ka[i] = k;
-        la[i] = p * PSA + k * RCA + (g ^ tr_swz<RCA>(k));
-        pa[i] = A + (k0 + k) * rowA + g * 2 + p;
-    }
-#pragma unroll
-    for (int i = 0; i < UB; i++) {
-        const int q = tid + i * NT;
-        const int k = q / (2 * RCB), c = q - k * (2 * RCB), p = c / RCB, g = c - p * RCB;
-        kb[i] = k;
-        lb[i] = 2 * PSA + p * PSB + k * RCB + (g ^ tr_swz<RCB>(k));
-        pb[i] = B + (k0 + k) * rowB + g * 2 + p;
-    }
-    u32x4 ra[UA], rb[UB];
-    auto load = [&](int64_t kk) {
-        if (kk + BK <= k1) {
-            const int64_t da = (kk - k0) * rowA, db = (kk - k0) * rowB;
-#pragma unroll
-            for (int i = 0; i < UA; i++) ra[i] = pa[i][da];
-#pragma unroll
-            for (int i = 0; i < UB; i++) rb[i] = pb[i][db];
-            return;
-        }
-#pragma unroll
-        for (int i = 0; i < UA; i++) ra[i] = pa[i][(std::min(kk + ka[i], k1 - 1) - k0 - ka[i]) * rowA];
-#pragma unroll
-        for (int i = 0; i < UB; i++) rb[i] = pb[i][(std::min(kk + kb[i], k1 - 1) - k0 - kb[i]) * rowB];
-    };
-    auto store = [&](int buf, int64_t kk) {
-        u32x4 *st = lds + buf * STAGE;
-        const u32x4 zero = u32x4{0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int i = 0; i < UA; i++) st[la[i]] = kk + ka[i] < k1 ? ra[i] : zero;
-#pragma unroll
-        for (int i = 0; i < UB; i++) st[lb[i]] = kk + kb[i] < k1 ? rb[i] : zero;
-    };
-
-    f32x16 hi[TM][TN], lo[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-        for (int j = 0; j < TN; j++) {
-            hi[i][j] = f32x16{};
-            lo[i][j] = f32x16{};
-        }
-
-    if (k0 < k1) {
-        load(k0);
-        store(0, k0);
-        if (k0 + BK < k1) load(k0 + BK);
-        __syncthreads();
-    }
-    int buf = 0;
-    for (int64_t kk = k0; kk < k1; kk += BK, buf ^= 1) {
-        if (kk + BK < k1) store(buf ^ 1, kk + BK);
-        if (kk + 2 * BK < k1) load(kk + 2 * BK);
-        const u32x4 *sAl = lds + buf * STAGE, *sBl = sAl + 2 * PSA;
-        u32x4 af[TM][2][2];
+        };
 #pragma unroll
         for (int i = 0; i < TM; i++)
 #pragma unroll
             for (int kh = 0; kh < 2; kh++)
 #pragma unroll
                 for (int p = 0; p < 2; p++) af[i][kh][p] = tr_frag<RCA>(sAl + p * PSA, wm * WTM + i * 32, kh, lane);
+        if constexpr (PIPE) {
+#pragma unroll
+            for (int j = 0; j < TN; j++) read_b(j);
+        }
 #pragma unroll
         for (int j = 0; j < TN; j++) {
-            u32x4 bf[2][2];
-#pragma unroll
-            for (int kh = 0; kh < 2; kh++)
-#pragma unroll
-                for (int p = 0; p < 2; p++) bf[kh][p] = tr_frag<RCB>(sBl + p * PSB, wn * WTN + j * 32, kh, lane);
+            if constexpr (!PIPE) read_b(j);
 #pragma unroll
             for (int i = 0; i < TM; i++) {
-                f32x16 l = lo[i][j], h = hi[i][j];
 #pragma unroll
-                for (int kh = 0; kh < 2; kh++) {
-                    l = mfma16(af[i][kh][1], bf[kh][0], l);
-                    l = mfma16(af[i][kh][0], bf[kh][1], l);
-                    h = mfma16(af[i][kh][0], bf[kh][0], h);
-                }
-                lo[i][j] = l;
-                hi[i][j] = h;
+                for (int kh = 0; kh < 2; kh++) c.mma3(i, j, af[i][kh][0], af[i][kh][1], bf[j][kh][0], bf[j][kh][1]);
             }
         }
-        __syncthreads();
+    };
+
+    int buf = 0;
+    if constexpr (PIPE) {
+        const int64_t nsteps = k0 < k1 ? (k1 - k0 + BK - 1) / BK : 0, nfull = k0 < k1 ? (k1 - k0) / BK : 0;
+        if (nsteps > 0) {
+            load(k0);
+            store(0, k0);
+            if (nsteps > 1) load(k0 + BK);
+            __syncthreads();
+        }
+        int64_t st = 0, kk = k0;
+        for (; st + 2 < nfull; st++, kk += BK, buf ^= 1) {  // the load of step st + 2 is whole
+            compute(buf);
+            store(buf ^ 1, kk + BK);
+            load_whole(kk + 2 * BK);
+            __builtin_amdgcn_sched_group_barrier(0x100, (TM + TN) * 8, 0);
+#pragma unroll
+            for (int m = 0; m < NMFMA; m++) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+                if (m % 3 == 2) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+                if (m >= NMFMA / 2 && m % 2 == 1) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+            }
+            __syncthreads();
+        }
+        for (; st < nsteps; st++, kk += BK, buf ^= 1) {
+            if (st + 1 < nsteps) store(buf ^ 1, kk + BK);
+            if (st + 2 < nsteps) load(kk + 2 * BK);
+            compute(buf);
+            __syncthreads();
+        }
+    } else {
+        if (k0 < k1) {
+            fetch_rows(k0);
+            load(k0);
+            store(0, k0);
+            if (k0 + BK < k1) load(k0 + BK);
+            __syncthreads();
+        }
+        for (int64_t kk = k0; kk < k1; kk += BK, buf ^= 1) {
+            if (kk + BK < k1) store(buf ^ 1, kk + BK);
+            if (kk + 2 * BK < k1) load(kk + 2 * BK);
+            compute(buf);
+            __syncthreads();
+        }
     }
 
-    const float inv = pow2f(-eA), invB = pow2f(-eB);
-    float *St = slab + ((int64_t)s * (gridDim.x / (S * tiles)) + t) * (int64_t)M * N;
-    const int fr = lane & 31, fh = lane >> 5;
-#pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-        for (int j = 0; j < TN; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int row = m0 + wm * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                St[(int64_t)row * N + n0 + wn * WTN + j * 32 + fr] =
-                    (hi[i][j][r] + lo[i][j][r] * LO_INV) * inv * invB;
-            }
+    // the slab: the plain epilogue, every row present (M % BM == 0: the launcher checks)
+    const float bv[TN] = {};
+    c.store(IC<1>{}, IC<0>{}, slab + ((int64_t)s * (gridDim.x / (S * tiles)) + t) * (int64_t)M * N, N, M, m0,
+            wm * WTM + 4 * (lane >> 5), n0 + wn * WTN + (lane & 31), pow2f(-eA), pow2f(-eB), bv);
 }
+
+#define H3_TN_ARGS                                                                                                  \
+    const uint32_t *__restrict__ amaxA, const uint32_t *__restrict__ amaxB, int64_t Kd, int M, int N, int64_t sA, \
+        int64_t sB, int64_t kc, int tiles_n, int tiles, int S, float *__restrict__ slab
+#define H3_TN_PASS amaxA, amaxB, Kd, M, N, sA, sB, kc, tiles_n, tiles, S, slab
+template <int BM, int BN, int WGM, int WGN>
+__global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tn(const float4 *__restrict__ A, const float4 *__restrict__ B,
+                                                          H3_TN_ARGS) {
+    h3_tn_body<BM, BN, WGM, WGN, false>(A, B, H3_TN_PASS, nullptr);
+}
+template <int BM, int BN, int WGM, int WGN, bool AQ = false, bool BQ = false>
+__global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tng(const float4 *__restrict__ A, const float4 *__restrict__ B,
+                                                           H3_TN_ARGS, const int32_t *__restrict__ bmap) {
+    h3_tn_body<BM, BN, WGM, WGN, true, AQ, BQ>(A, B, H3_TN_PASS, bmap);
+}
+template <int BM, int BN, int WGM, int WGN>
+__global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tnp(const float4 *__restrict__ A, const float4 *__restrict__ B,
+                                                           H3_TN_ARGS) {
+    h3_tn_body<BM, BN, WGM, WGN, false, false, false, false, true>(A, B, H3_TN_PASS, nullptr);
+}
+template <int BM, int BN, int WGM, int WGN>
+__global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tnq(const u32x4 *__restrict__ A, const u32x4 *__restrict__ B,
+                                                           H3_TN_ARGS) {
+    h3_tn_body<BM, BN, WGM, WGN, false, false, false, true>(reinterpret_cast<const float4 *>(A),
+                                                            reinterpret_cast<const float4 *>(B), H3_TN_PASS, nullptr);
+}
+#undef H3_TN_ARGS
+#undef H3_TN_PASS
 
 template <int BM, int BN, int WGM, int WGN, bool PIPE>
 hipError_t nt_launch(const float *A, const u32x4 *B, const uint32_t *amaxA, const uint32_t *amaxB, int64_t M, int N,

@@ -13,33 +13,25 @@
 // by the first MFMA that needs them (the MFMAs still in the pipe cover it).
 //
 // Layouts as merlin_h3.hip's k_h3_ntg: operand rows of K/8 groups x (hi, lo) x 8 f16 (h3_split), a k step (32
-// values) = 8 16-B chunks per row; LDS image rows of 8 chunks, chunk c of row r at slot c ^ ((r >> 1) & 7), the
-// permutation applied to the DMA's global source address (a DMA writes lane-linear).
+// values) = 8 16-B chunks per row; LDS image rows of 8 chunks, chunk c of row r at slot c ^ g_swz(r)
+// (merlin_h3_tile.h), the permutation applied to the DMA's global source address (a DMA writes lane-linear).
+// The accumulator tile with its epilogues (H3Tile) and the TN kernel's transposed fragment read come from
+// merlin_h3_tile.h, shared with merlin_h3.hip's TN body.
 #include <algorithm>
-#include <type_traits>
 
+#include "merlin_h3_tile.h"
 #include "merlin_internal.h"
 
 namespace merlin {
 namespace {
 
-typedef _Float16 p_f16x8 __attribute__((ext_vector_type(8)));
-typedef float p_f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t p_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ p_f32x16 p_mfma(const p_u32x4 a, const p_u32x4 b, p_f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(p_f16x8, a), __builtin_bit_cast(p_f16x8, b), c, 0,
-                                                   0, 0);
-}
-__device__ __forceinline__ int p_swz(int r) { return (r >> 1) & 7; }
+// the vector types, mfma16, g_swz, IC, the accumulator tile H3Tile and the TN fragment read: merlin_h3_tile.h
 // a lo plane fragment (8 f16 at 2^11 x their value) back at scale: v_pk_mul_f16 x 4, exact unless the result is
 // subnormal (then rounded to the f16 subnormal grid, 2^-24)
-__device__ __forceinline__ p_u32x4 p_unscale(const p_u32x4 x) {
-    return __builtin_bit_cast(p_u32x4, __builtin_bit_cast(p_f16x8, x) * (_Float16)H3_LO_INV);
+__device__ __forceinline__ u32x4 p_unscale(const u32x4 x) {
+    return __builtin_bit_cast(u32x4, __builtin_bit_cast(f16x8, x) * (_Float16)H3_LO_INV);
 }
 
-template <int V>
-using IC = std::integral_constant<int, V>;
 template <int N, int I = 0, class F>
 __device__ __forceinline__ void static_for(F &&f) {
     if constexpr (I < N) {
@@ -48,14 +40,14 @@ __device__ __forceinline__ void static_for(F &&f) {
     }
 }
 
-typedef __attribute__((address_space(3))) p_u32x4 lds_u32x4;
+typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
 // one 16-B LDS fragment read (a plain load: the k loop is unrolled, so the compiler's waits are exact counts)
-__device__ __forceinline__ void lds_rd(p_u32x4 &d, uint32_t addr) { d = *(const lds_u32x4 *)(uintptr_t)addr; }
+__device__ __forceinline__ void lds_rd(u32x4 &d, uint32_t addr) { d = *(const lds_u32x4 *)(uintptr_t)addr; }
 
 // ---------------------------------------------------------------------------------------------------------------
-// What the four NT bodies below (pq_tile, pqg_tile, pq_walk, pqg_walk) share: a wave's accumulators, the fragment
-// reads and MFMAs of a half step over a staged k step, and the epilogues.  A body keeps what is its own: where its
-// DMAs read, its ring schedule and its waits.
+// What the four NT bodies below (pq_tile, pqg_tile, pq_walk, pqg_walk) share besides the accumulator tile and its
+// epilogues (H3Tile, merlin_h3_tile.h): the fragment reads and MFMAs of a half step over a staged k step.  A body
+// keeps what is its own: where its DMAs read, its ring schedule and its waits.
 // ONE (round 6): one accumulator per tile -- the lo planes (stored 2^11 up) brought back to scale in registers
 // (v_pk_mul_f16 by 2^-11: exact while the result stays normal, f16 subnormals kept) so all three products of a k
 // step add into the same fp32 accumulator: half the accumulator registers, hence twice the tile area per byte staged.
@@ -63,10 +55,11 @@ __device__ __forceinline__ void lds_rd(p_u32x4 &d, uint32_t addr) { d = *(const 
 // tests/test_gpu_h3.py like theirs.
 // ORD: the order of a half step's MFMAs, see mf.
 template <int BM, int BN, int WGM, int WGN, bool ONE = false, int ORD = 0>
-struct PCore {
-    static constexpr int NT = 64 * WGM * WGN;
-    static constexpr int WTM = BM / WGM, WTN = BN / WGN;
-    static constexpr int TM = WTM / 32, TN = WTN / 32;
+struct PCore : H3Tile<BM, BN, WGM, WGN, ONE> {
+    using TL = H3Tile<BM, BN, WGM, WGN, ONE>;
+    using TL::hi;
+    using TL::lo;
+    static constexpr int NT = TL::NT, WTM = TL::WTM, WTN = TL::WTN, TM = TL::TM, TN = TL::TN;
     static constexpr int NR = 2 * (TM + TN), NM = 3 * TM * TN;  // fragment reads / MFMAs per half step
     static_assert(NM >= NR, "a read behind every MFMA");
     static constexpr int GA = BM * 8 / NT, GB = BN * 8 / NT, G = GA + GB;  // DMA instructions per thread and k step
@@ -76,9 +69,8 @@ struct PCore {
     static constexpr int CS = TM * TN * 16;  // C stores per wave and tile
 
     struct Frag {
-        p_u32x4 a[TM][2], b[TN][2];  // [tile][plane]
+        u32x4 a[TM][2], b[TN][2];  // [tile][plane]
     };
-    p_f32x16 hi[TM][TN], lo[TM][TN];
     // fragment addresses (bytes, stage 0): A tile i / B tile j at half kh, plane p -> row r, chunk 2 (2 kh + fh) + p
     uint32_t adA[2][2], adB[2][2];  // [kh][p], tile 0; tile i is +32 i rows (same swizzle)
 
@@ -89,19 +81,10 @@ struct PCore {
 #pragma unroll
             for (int p = 0; p < 2; p++) {
                 const int c = 2 * (2 * kh + fh) + p;
-                adA[kh][p] = lds0 + (uint32_t)(ra * 8 + (c ^ p_swz(ra))) * 16u;
-                adB[kh][p] = lds0 + (uint32_t)(rb * 8 + (c ^ p_swz(rb))) * 16u;
+                adA[kh][p] = lds0 + (uint32_t)(ra * 8 + (c ^ g_swz(ra))) * 16u;
+                adB[kh][p] = lds0 + (uint32_t)(rb * 8 + (c ^ g_swz(rb))) * 16u;
             }
-        zero();
-    }
-    __device__ __forceinline__ void zero() {
-#pragma unroll
-        for (int i = 0; i < TM; i++)
-#pragma unroll
-            for (int j = 0; j < TN; j++) {
-                hi[i][j] = p_f32x16{};
-                lo[i][j] = p_f32x16{};
-            }
+        this->zero();
     }
     // the k-th of the NR fragment reads of half KH of the stage at byte offset so into g (k, KH compile-time: no
     // runtime-indexed fragment arrays)
@@ -122,17 +105,17 @@ struct PCore {
         constexpr int i = tl / TN, j = tl % TN;
         if constexpr (ONE) {  // u: f's lo planes at scale
             if constexpr (pr == 0)
-                hi[i][j] = p_mfma(u.a[i][1], f.b[j][0], hi[i][j]);
+                hi[i][j] = mfma16(u.a[i][1], f.b[j][0], hi[i][j]);
             else if constexpr (pr == 1)
-                hi[i][j] = p_mfma(f.a[i][0], u.b[j][1], hi[i][j]);
+                hi[i][j] = mfma16(f.a[i][0], u.b[j][1], hi[i][j]);
             else
-                hi[i][j] = p_mfma(f.a[i][0], f.b[j][0], hi[i][j]);
+                hi[i][j] = mfma16(f.a[i][0], f.b[j][0], hi[i][j]);
         } else if constexpr (pr == 0)
-            lo[i][j] = p_mfma(f.a[i][1], f.b[j][0], lo[i][j]);
+            lo[i][j] = mfma16(f.a[i][1], f.b[j][0], lo[i][j]);
         else if constexpr (pr == 1)
-            lo[i][j] = p_mfma(f.a[i][0], f.b[j][1], lo[i][j]);
+            lo[i][j] = mfma16(f.a[i][0], f.b[j][1], lo[i][j]);
         else
-            hi[i][j] = p_mfma(f.a[i][0], f.b[j][0], hi[i][j]);
+            hi[i][j] = mfma16(f.a[i][0], f.b[j][0], hi[i][j]);
     }
     // half step: the NM MFMAs on f, with the NR reads of g (stage offset so, half KH) one behind each of the first NR
     // (sched_group_barrier: MFMA, read, MFMA, read, ...), so the reads of a half are waited for once, by the first
@@ -173,79 +156,6 @@ struct PCore {
         asm volatile("" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
     }
-
-    __device__ __forceinline__ float acc(int i, int j, int r) const {
-        return ONE ? hi[i][j][r] : hi[i][j][r] + lo[i][j][r] * H3_LO_INV;
-    }
-    // The plain epilogue: C[row][col] = acc x inv x invB (EPI 1: + bias, ReLU) over the wave's part of the tile at
-    // row m0: rows m0 + rw + ..., rw = wm WTM + 4 fh; columns col0 + 32 j, col0 = n0 + wn WTN + fr; bv[j] their bias.
-    // FULL: every row of the tile exists, so the stores are unconditional (a walk counts them in its vmcnt waits)
-    template <class FULL, class EPI_>
-    __device__ __forceinline__ void store(FULL, EPI_, float *Ct, int64_t N, int64_t M, int64_t m0, int rw, int col0,
-                                          float inv, float invB, const float (&bv)[TN]) const {
-#pragma unroll
-        for (int j = 0; j < TN; j++) {
-            const int col = col0 + j * 32;
-#pragma unroll
-            for (int i = 0; i < TM; i++) {
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int64_t row = m0 + rw + i * 32 + (r & 3) + 8 * (r >> 2);
-                    if (FULL::value || row < M) {
-                        const float v = acc(i, j, r) * inv * invB;
-                        Ct[row * N + col] = EPI_::value == 1 ? relu_nan(v + bv[j]) : v;
-                    }
-                }
-            }
-        }
-    }
-    // The heads epilogue (merlin_h3.hip's h3_ntp_body EPI 2): bias + ReLU as above, and of the stored values the
-    // policy / value heads' partial dot products over the wave's 64 columns (wv[o][j]: head row o's weights of the
-    // lane's columns), two per lane into part[row][4] (rp: rw again, for the partials' rows): CS + 2 TM stores per
-    // wave.  Per i: the 16 rows x 4 head outputs of this lane's two columns, then a reduce-scatter over the 32 column
-    // lanes of the half-wave (xor 16 .. 1, each step keeping the half of the values its lane bit selects): lane fr
-    // ends with output o = fr >> 3 of rows r = 2 (fr & 7) + k, k < 2.  (The reduce-scatter is written here and in
-    // h3_ntp_body, not as a function of its own: as one, the walk's heads kernel needs scratch.)
-    template <class FULL>
-    __device__ __forceinline__ void store_heads(FULL, float *Ct, float *part, int64_t N, int64_t M, int64_t m0, int rw,
-                                                int rp, int col0, int fr, float inv, float invB,
-                                                const float (&bv)[TN], const float (&wv)[4][TN]) const {
-        static_assert(TN == 2 && WTN == 64, "heads epilogue: a wave tile 64 columns wide");
-#pragma unroll
-        for (int i = 0; i < TM; i++) {
-            float pv[64];  // [o][r]
-#pragma unroll
-            for (int q = 0; q < 64; q++) pv[q] = 0.0f;
-#pragma unroll
-            for (int j = 0; j < TN; j++) {
-                const int col = col0 + j * 32;
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int64_t row = m0 + rw + i * 32 + (r & 3) + 8 * (r >> 2);
-                    const float v = relu_nan(acc(i, j, r) * inv * invB + bv[j]);
-                    if (FULL::value || row < M) Ct[row * N + col] = v;
-#pragma unroll
-                    for (int o = 0; o < 4; o++) pv[o * 16 + r] += v * wv[o][j];
-                }
-            }
-#pragma unroll
-            for (int c = 64, off = 16; off >= 1; c >>= 1, off >>= 1) {
-                const bool up = (fr & off) != 0;
-#pragma unroll
-                for (int k = 0; k < c / 2; k++) {
-                    const float send = up ? pv[k] : pv[k + c / 2], keep = up ? pv[k + c / 2] : pv[k];
-                    pv[k] = keep + __shfl_xor(send, off);
-                }
-            }
-            const int o = fr >> 3;
-#pragma unroll
-            for (int k = 0; k < 2; k++) {
-                const int r = 2 * (fr & 7) + k;
-                const int64_t row = m0 + rp + i * 32 + (r & 3) + 8 * (r >> 2);
-                if (FULL::value || row < M) part[row * 4 + o] = pv[k];
-            }
-        }
-    }
 };
 
 // NS: LDS stages of the DMA ring (NS - 1 k steps in flight).  3: 120 KB at 128 x 192; 4 (round 6): 160 KB, the whole
@@ -254,7 +164,7 @@ struct PCore {
 // (pq_tile: the body of k_h3_pq's one-tile form, a block per tile; the kernel and its persistent form are defined
 // behind the walks, at the end of this namespace)
 template <int BM, int BN, int WGM, int WGN, int EPI, int NK, int NS, bool ONE, int ORD>
-__device__ __forceinline__ void pq_tile(const p_u32x4 *__restrict__ A, const p_u32x4 *__restrict__ B,
+__device__ __forceinline__ void pq_tile(const u32x4 *__restrict__ A, const u32x4 *__restrict__ B,
                                         const uint32_t *__restrict__ amaxA, const uint32_t *__restrict__ amaxB,
                                         int64_t M, int N, int K, int64_t sA, int64_t sB,
                                         const float *__restrict__ bias, float *__restrict__ C, int64_t sC,
@@ -264,7 +174,7 @@ __device__ __forceinline__ void pq_tile(const p_u32x4 *__restrict__ A, const p_u
     constexpr int NT = P::NT, WTM = P::WTM, WTN = P::WTN, TN = P::TN, NR = P::NR, G = P::G, STG = P::STG;
     constexpr uint32_t STG_B = P::STG_B;
     static_assert(NS >= 2 && NS <= 4, "ring depth");
-    __shared__ p_u32x4 lds[NS * STG];
+    __shared__ u32x4 lds[NS * STG];
 
     const int t = blockIdx.y;
     const int L = xcd_tile(blockIdx.x, gridDim.x);
@@ -279,27 +189,27 @@ __device__ __forceinline__ void pq_tile(const p_u32x4 *__restrict__ A, const p_u
     const int eA = h3_exp(load_amax(amaxA + t)), eB = h3_exp(load_amax(amaxB + t));
     // DMA sources as 32-bit chunk offsets from the uniform row-block bases (6 VGPRs, not 6 64-bit pointers): A's
     // block rows m0.. and B's n0.. (the last A rows clamped to M - 1: read, never stored)
-    const p_u32x4 *baseA = A + t * sA + m0 * row_ch, *baseB = B + t * sB + (int64_t)n0 * row_ch;
+    const u32x4 *baseA = A + t * sA + m0 * row_ch, *baseB = B + t * sB + (int64_t)n0 * row_ch;
     uint32_t off[G];
 #pragma unroll
     for (int i = 0; i < G; i++) {
-        const int q = i * NT + tid, r = q >> 3, c = (q & 7) ^ p_swz(r);
+        const int q = i * NT + tid, r = q >> 3, c = (q & 7) ^ g_swz(r);
         off[i] = r < BM ? (uint32_t)(std::min<int64_t>(r, M - 1 - m0) * row_ch + c) : (uint32_t)((r - BM) * row_ch + c);
     }
     typedef __attribute__((address_space(3))) void lds_void;
     typedef __attribute__((address_space(1))) void gbl_void;
     auto issue = [&](int kt, int st) __attribute__((always_inline)) {
-        p_u32x4 *base = lds + st * STG + w * 64;
+        u32x4 *base = lds + st * STG + w * 64;
 #pragma unroll
         for (int i = 0; i < G; i++) {
             const int q0 = i * NT;  // instruction-uniform: which operand
-            const p_u32x4 *b = (q0 >> 3) < BM ? baseA : baseB;
+            const u32x4 *b = (q0 >> 3) < BM ? baseA : baseB;
             __builtin_amdgcn_global_load_lds((gbl_void *)(b + off[i] + kt * 8), (lds_void *)(base + i * NT), 16, 0, 0);
         }
     };
 
     const int fr = lane & 31, fh = lane >> 5;
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) p_u32x4 *)lds;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) u32x4 *)lds;
     P c;
     c.init(lds0, wm, wn, fr, fh);
 
@@ -341,8 +251,9 @@ __device__ __forceinline__ void pq_tile(const p_u32x4 *__restrict__ A, const p_u
 // TN over plane operands with LDS-DMA staging (round 5; the weight gradient dz^T a3, merlin_h3_gemm_tn_gather_planes
 // with cfg 20): slab[s][t][m][n] = sum over the split's rows k of A[t][k][m] B[t][k][n], A planes [Kd][M/8][2][8]
 // (k_head_bwd's dz), B planes gathered by 64-column chunks (row k's chunk j is row bmap[k * N / 64 + j] of B seen
-// as [*][64]: conv3's representatives).  The LDS images are k_h3_tn's -- per operand and plane [32 k rows][RC chunks
-// of 8 columns], chunk c of row r at c ^ swz(r), fragments k-contiguous through ds_read_b64_tr_b16 -- but filled by
+// as [*][64]: conv3's representatives).  The LDS images are h3_tn_body's (merlin_h3_tile.h) -- per operand and plane
+// [32 k rows][RC chunks of 8 columns], chunk c of row r at c ^ tr_swz(r), fragments k-contiguous through
+// ds_read_b64_tr_b16 (tr_off / tr_read / tr_pack) -- but filled by
 // DMA three k steps deep: a DMA writes its 64 lanes' 16-B chunks lane-linear, so each lane's source is the chunk
 // whose image slot that is (the swizzle and the plane deinterleave are in the source addresses).  B's chunk rows
 // come from bmap through a 3-slot LDS ring, itself filled by DMA four steps ahead, so the data DMA's addresses need
@@ -373,26 +284,17 @@ __device__ __forceinline__ void p_dma4(const void *src, uint32_t lds) {
                  : "memory");
 }
 
-template <int RC>
-__device__ __forceinline__ int p_tr_swz(int row) {
-    static_assert(RC % 16 == 0 || RC == 24 || RC == 8, "row chunks");  // 8 (128-B rows): as 24
-    return RC % 16 == 0 ? (row & 3) << 2 : ((row >> 1) & 1) << 2;
-}
-typedef __bf16 p_bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 p_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) p_bf16x4 lds_p_bf16x4;
 typedef __attribute__((address_space(3))) int32_t lds_i32;
 
 template <int BM, int BN, int WGM, int WGN>
-__global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tq(const p_u32x4 *__restrict__ A, const p_u32x4 *__restrict__ B,
+__global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tq(const u32x4 *__restrict__ A, const u32x4 *__restrict__ B,
                                                           const uint32_t *__restrict__ amaxA,
                                                           const uint32_t *__restrict__ amaxB, int64_t Kd, int M,
                                                           int N, int64_t sA, int64_t sB, int64_t kc, int tiles_n,
                                                           int tiles, int S, float *__restrict__ slab,
                                                           const int32_t *__restrict__ bmap) {
-    constexpr int NT = 64 * WGM * WGN, NW = NT / 64;
-    constexpr int WTM = BM / WGM, WTN = BN / WGN;
-    constexpr int TM = WTM / 32, TN = WTN / 32;
+    using TL = H3Tile<BM, BN, WGM, WGN>;
+    constexpr int NT = TL::NT, NW = NT / 64, WTM = TL::WTM, WTN = TL::WTN, TM = TL::TM, TN = TL::TN;
     constexpr int RCA = BM / 8, RCB = BN / 8;
     constexpr int PSA = 32 * RCA, PSB = 32 * RCB;  // chunks per plane image
     constexpr int STG = 2 * (PSA + PSB);
@@ -404,7 +306,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tq(const p_u32x4 *__restr
     static_assert(32 * JB <= XS, "index slot");
     constexpr int NF = 2 * (TM + TN);             // fragments per half step (tiles x planes)
     constexpr int NR = 2 * NF, NM = 3 * TM * TN;  // tr reads (two per fragment) / MFMAs per half step
-    __shared__ p_u32x4 lds[3 * STG];
+    __shared__ u32x4 lds[3 * STG];
     __shared__ int32_t ixr[3 * XS];
 
     const int P = xcd_tile(blockIdx.x, gridDim.x);
@@ -417,8 +319,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tq(const p_u32x4 *__restr
     const int wm = w / WGN, wn = w - (w / WGN) * WGN;
     const int nc = N / 64, j0 = n0 / 64;
     const int64_t rowA = M / 4;  // chunks per A row
-    const p_u32x4 *At = A + t * sA, *Bt = B + t * sB;
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) p_u32x4 *)lds;
+    const u32x4 *At = A + t * sA, *Bt = B + t * sB;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) u32x4 *)lds;
     const uint32_t ix0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int32_t *)ixr;
     const uint32_t wbase = (uint32_t)__builtin_amdgcn_readfirstlane(w) * 64u;  // the wave's first slot
 
@@ -428,7 +330,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tq(const p_u32x4 *__restr
 #pragma unroll
     for (int i = 0; i < GA; i++) {
         const int q = i * NT + tid, p = q / PSA, rem = q - p * PSA, r = rem / RCA, cs = rem - r * RCA;
-        const int c = cs ^ p_tr_swz<RCA>(r);
+        const int c = cs ^ tr_swz<RCA>(r);
         ra[i] = r;
         oa[i] = (uint32_t)((m0 / 8 + c) * 2 + p);
     }
@@ -436,7 +338,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tq(const p_u32x4 *__restr
     for (int i = 0; i < GB; i++) {
         const int q = (GA + i) * NT + tid - 2 * PSA, p = q / PSB, rem = q - p * PSB, r = rem / RCB,
                   cs = rem - r * RCB;
-        const int c = cs ^ p_tr_swz<RCB>(r), col = 8 * c;
+        const int c = cs ^ tr_swz<RCB>(r), col = 8 * c;
         rb[i] = r;
         xb[i] = r * JB + (col >> 6);
         gp[i] = (uint32_t)(((col & 63) >> 3) * 2 + p);
@@ -461,22 +363,21 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tq(const p_u32x4 *__restr
         const bool full = kk + 32 <= k1;  // block-uniform
 #pragma unroll
         for (int i = 0; i < GA; i++) {
-            const p_u32x4 *src = full || kk + ra[i] < k1 ? At + (kk + ra[i]) * rowA + oa[i]
-                                                          : reinterpret_cast<const p_u32x4 *>(p_zero16);
+            const u32x4 *src = full || kk + ra[i] < k1 ? At + (kk + ra[i]) * rowA + oa[i]
+                                                          : reinterpret_cast<const u32x4 *>(p_zero16);
             p_dma16(src, base + (uint32_t)(i * NT) * 16u);
         }
 #pragma unroll
         for (int i = 0; i < GB; i++) {
-            const p_u32x4 *src = full || kk + rb[i] < k1 ? Bt + (int64_t)x[i] * 16 + gp[i]
-                                                          : reinterpret_cast<const p_u32x4 *>(p_zero16);
+            const u32x4 *src = full || kk + rb[i] < k1 ? Bt + (int64_t)x[i] * 16 + gp[i]
+                                                          : reinterpret_cast<const u32x4 *>(p_zero16);
             p_dma16(src, base + (uint32_t)((GA + i) * NT) * 16u);
         }
     };
 
     // fragment reads: fragment f < NF (A tiles x planes, then B tiles x planes), its two transposed halves
-    const int fg = lane >> 4, fq = (lane >> 2) & 3, fp = lane & 3;
     struct Frag {
-        p_bf16x4 v[NF][2];
+        bf16x4 v[NF][2];
     };
     auto rd = [&](Frag &g, auto K_, uint32_t so, auto KH) __attribute__((always_inline)) {
         constexpr int k = decltype(K_)::value, kh = decltype(KH)::value, f = k >> 1, h2 = k & 1;
@@ -485,33 +386,21 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tq(const p_u32x4 *__restr
         constexpr int RC = isA ? RCA : RCB;
         const int col0 = isA ? wm * WTM + tile * 32 : wn * WTN + tile * 32;
         const uint32_t img = lds0 + so + (uint32_t)(isA ? pl * PSA : 2 * PSA + pl * PSB) * 16u;
-        const int chunk = ((col0 + 16 * (fg & 1)) >> 3) + (fp >> 1);
-        const int row = 16 * kh + 8 * (fg >> 1) + 4 * h2 + fq;
-        const uint32_t off = img + (uint32_t)((row * RC + (chunk ^ p_tr_swz<RC>(row))) * 16 + (fp & 1) * 8);
-        g.v[f][h2] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p_bf16x4 *)(uintptr_t)off);
+        g.v[f][h2] = tr_read((const lds_char *)(uintptr_t)(img + (uint32_t)tr_off<RC>(col0, kh, h2, lane)));
     };
-    auto frag = [](const Frag &g, int f) __attribute__((always_inline)) {
-        return __builtin_bit_cast(p_u32x4, p_bf16x8{g.v[f][0][0], g.v[f][0][1], g.v[f][0][2], g.v[f][0][3],
-                                                   g.v[f][1][0], g.v[f][1][1], g.v[f][1][2], g.v[f][1][3]});
-    };
-    p_f32x16 hi[TM][TN], lo[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-        for (int j = 0; j < TN; j++) {
-            hi[i][j] = p_f32x16{};
-            lo[i][j] = p_f32x16{};
-        }
+    auto frag = [](const Frag &g, int f) __attribute__((always_inline)) { return tr_pack(g.v[f][0], g.v[f][1]); };
+    TL c;
+    c.zero();
     // MFMA m of a half step: tile (i, j) = (m / (3 TN), (m / 3) % TN), product m % 3 (k_h3_tn's order per tile)
     auto mf = [&](const Frag &f, auto M_) __attribute__((always_inline)) {
         constexpr int m = decltype(M_)::value, i = m / (3 * TN), j = (m / 3) % TN, pr = m % 3;
         constexpr int fa0 = 2 * i, fa1 = 2 * i + 1, fb0 = 2 * TM + 2 * j, fb1 = 2 * TM + 2 * j + 1;
         if constexpr (pr == 0)
-            lo[i][j] = p_mfma(frag(f, fa1), frag(f, fb0), lo[i][j]);
+            c.lo[i][j] = mfma16(frag(f, fa1), frag(f, fb0), c.lo[i][j]);
         else if constexpr (pr == 1)
-            lo[i][j] = p_mfma(frag(f, fa0), frag(f, fb1), lo[i][j]);
+            c.lo[i][j] = mfma16(frag(f, fa0), frag(f, fb1), c.lo[i][j]);
         else
-            hi[i][j] = p_mfma(frag(f, fa0), frag(f, fb0), hi[i][j]);
+            c.hi[i][j] = mfma16(frag(f, fa0), frag(f, fb0), c.hi[i][j]);
     };
     constexpr int RPM = (NR + NM - 1) / NM;  // reads behind each MFMA
     auto half = [&](const Frag &f, Frag &g, uint32_t so, auto KH) __attribute__((always_inline)) {
@@ -577,18 +466,10 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tq(const p_u32x4 *__restr
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the padded steps' DMAs drained before the block ends
 
-    const float inv = pow2f(-eA), invB = pow2f(-eB);
-    float *St = slab + ((int64_t)s * (gridDim.x / (S * tiles)) + t) * (int64_t)M * N;
-    const int fr = lane & 31, fh = lane >> 5;
-#pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-        for (int j = 0; j < TN; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int row = m0 + wm * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                St[(int64_t)row * N + n0 + wn * WTN + j * 32 + fr] = (hi[i][j][r] + lo[i][j][r] * H3_LO_INV) * inv * invB;
-            }
+    // the slab: the plain epilogue, every row present (M % BM == 0: the launcher checks)
+    const float bv[TN] = {};
+    c.store(IC<1>{}, IC<0>{}, slab + ((int64_t)s * (gridDim.x / (S * tiles)) + t) * (int64_t)M * N, N, M, m0,
+            wm * WTM + 4 * (lane >> 5), n0 + wn * WTN + (lane & 31), pow2f(-eA), pow2f(-eB), bv);
 }
 
 
@@ -602,7 +483,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_tq(const p_u32x4 *__restr
 // vmcnt before LDS reads).  The same products in the same order as k_h3_ntpg: the same bits.
 // (pqg_tile: the body of k_h3_pqg's one-tile form)
 template <int BM, int BN, int WGM, int WGN, int EPI>
-__device__ __forceinline__ void pqg_tile(const p_u32x4 *__restrict__ A, const p_u32x4 *__restrict__ B,
+__device__ __forceinline__ void pqg_tile(const u32x4 *__restrict__ A, const u32x4 *__restrict__ B,
                                          const uint32_t *__restrict__ amaxA, const uint32_t *__restrict__ amaxB,
                                          int64_t M, int N, int64_t sA, int64_t sB, const float *__restrict__ bias,
                                          float *__restrict__ C, int64_t sC, int tiles_n,
@@ -614,7 +495,7 @@ __device__ __forceinline__ void pqg_tile(const p_u32x4 *__restrict__ A, const p_
     constexpr int NT = P::NT, WTM = P::WTM, WTN = P::WTN, TN = P::TN, NR = P::NR, GA = P::GA, GB = P::GB, G = P::G;
     constexpr int STG = P::STG;
     constexpr uint32_t STG_B = P::STG_B;
-    __shared__ p_u32x4 lds[3 * STG];
+    __shared__ u32x4 lds[3 * STG];
     __shared__ int32_t gmap[BM * KC];
 
     const int t = blockIdx.y;
@@ -630,7 +511,7 @@ __device__ __forceinline__ void pqg_tile(const p_u32x4 *__restrict__ A, const p_
         gmap[e] = amap[std::min<int64_t>(m0 + r, M - 1) * KC + (e - r * KC)];
     }
     __syncthreads();
-    const p_u32x4 *At = A + t * sA, *baseB = B + t * sB + (int64_t)n0 * (K / 4);
+    const u32x4 *At = A + t * sA, *baseB = B + t * sB + (int64_t)n0 * (K / 4);
     int ga[GA];       // gmap entry base r * KC of the thread's A slots
     uint32_t ca[GA];  // their chunk within a k step
     uint32_t offB[GB];
@@ -638,14 +519,14 @@ __device__ __forceinline__ void pqg_tile(const p_u32x4 *__restrict__ A, const p_
     for (int i = 0; i < GA; i++) {
         const int q = i * NT + tid, r = q >> 3;
         ga[i] = r * KC;
-        ca[i] = (uint32_t)((q & 7) ^ p_swz(r));
+        ca[i] = (uint32_t)((q & 7) ^ g_swz(r));
     }
 #pragma unroll
     for (int i = 0; i < GB; i++) {
         const int q = i * NT + tid, r = q >> 3;
-        offB[i] = (uint32_t)(r * (K / 4) + ((q & 7) ^ p_swz(r)));
+        offB[i] = (uint32_t)(r * (K / 4) + ((q & 7) ^ g_swz(r)));
     }
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) p_u32x4 *)lds;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) u32x4 *)lds;
     const uint32_t gm0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int32_t *)gmap;
     const uint32_t wbase = (uint32_t)__builtin_amdgcn_readfirstlane(w) * 64u;
     // the chunk rows of step kt's A slots (plain LDS loads, read a step ahead of their issue)
@@ -715,7 +596,7 @@ __device__ __forceinline__ void pqg_tile(const p_u32x4 *__restrict__ A, const p_
             wv[o][j] = o < nh ? x : 0.0f;
         });
         float *part = hpart + ((int64_t)(t * tiles_n + tn) * WGN + wn) * M * 4;
-        c.store_heads(IC<0>{}, Ct, part, N, M, m0, rw, rw, col0, fr, inv, invB, bv, wv);
+        c.store_heads(IC<0>{}, IC<2>{}, Ct, part, N, M, m0, rw, rw, col0, fr, inv, invB, bv, wv);
     } else {
         c.store(IC<0>{}, IC<EPI>{}, Ct, N, M, m0, rw, col0, inv, invB, bv);
     }
@@ -767,7 +648,7 @@ __device__ __forceinline__ PItem p_item(int v, int W, int tiles, int tiles_n, in
 }
 
 template <int BM, int BN, int WGM, int WGN, int EPI, int NK, int ORD>
-__device__ __forceinline__ void pq_walk(const p_u32x4 *__restrict__ A, const p_u32x4 *__restrict__ B,
+__device__ __forceinline__ void pq_walk(const u32x4 *__restrict__ A, const u32x4 *__restrict__ B,
                                         const uint32_t *__restrict__ amaxA, const uint32_t *__restrict__ amaxB,
                                         int64_t M, int N, int K, int64_t sA, int64_t sB,
                                         const float *__restrict__ bias, float *__restrict__ C, int64_t sC,
@@ -781,7 +662,7 @@ __device__ __forceinline__ void pq_walk(const p_u32x4 *__restrict__ A, const p_u
     constexpr int CARRY = S + G < 63 ? S + G : 63;  // the vmcnt field's largest value
     const int N_ = N;
     static_assert(NK >= 4, "the look-ahead's k steps");
-    __shared__ p_u32x4 lds[3 * STG];
+    __shared__ u32x4 lds[3 * STG];
 
     int v = blockIdx.x;
     const int nb = gridDim.x;
@@ -789,7 +670,7 @@ __device__ __forceinline__ void pq_walk(const p_u32x4 *__restrict__ A, const p_u
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int wm = w / WGN, wn = w - (w / WGN) * WGN;
     const int64_t row_ch = K / 4;
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) p_u32x4 *)lds;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) u32x4 *)lds;
     const uint32_t wbase = (uint32_t)__builtin_amdgcn_readfirstlane(w) * 64u * 16u;
 
     PItem cur = p_item(v, W, tiles, tiles_n, BM, BN);
@@ -806,16 +687,16 @@ __device__ __forceinline__ void pq_walk(const p_u32x4 *__restrict__ A, const p_u
     auto set_offA = [&](const PItem &it) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < GA; i++) {
-            const int q = i * NT + tid, r = q >> 3, c = (q & 7) ^ p_swz(r);
+            const int q = i * NT + tid, r = q >> 3, c = (q & 7) ^ g_swz(r);
             offA[i] = (uint32_t)(std::min<int64_t>(r, M - 1 - it.m0) * row_ch + c) * 16u;
         }
     };
 #pragma unroll
     for (int i = 0; i < GB; i++) {
-        const int q = (GA + i) * NT + tid, r = q >> 3, c = (q & 7) ^ p_swz(r);
+        const int q = (GA + i) * NT + tid, r = q >> 3, c = (q & 7) ^ g_swz(r);
         offB[i] = (uint32_t)((r - BM) * row_ch + c) * 16u;
     }
-    const p_u32x4 *bA, *bB;  // the item the DMAs are issued for
+    const u32x4 *bA, *bB;  // the item the DMAs are issued for
     auto set_base = [&](const PItem &it) __attribute__((always_inline)) {
         bA = A + it.t * sA + it.m0 * row_ch;
         bB = B + it.t * sB + (int64_t)it.n0 * row_ch;
@@ -911,7 +792,7 @@ __device__ __forceinline__ void pq_walk(const p_u32x4 *__restrict__ A, const p_u
 // (BM x 9 chunk rows) is itself fetched by DMA, into the other of two LDS buffers, in the middle of the tile before:
 // three 4-byte DMAs per thread behind step 10's data, which the waits of steps 8 and 9 let stay in flight.
 template <int BM, int BN, int WGM, int WGN, int EPI>
-__device__ __forceinline__ void pqg_walk(const p_u32x4 *__restrict__ A, const p_u32x4 *__restrict__ B,
+__device__ __forceinline__ void pqg_walk(const u32x4 *__restrict__ A, const u32x4 *__restrict__ B,
                                          const uint32_t *__restrict__ amaxA, const uint32_t *__restrict__ amaxB,
                                          int64_t M, int N, int64_t sA, int64_t sB, const float *__restrict__ bias,
                                          float *__restrict__ C, int64_t sC, int tiles_n, int tiles, int W,
@@ -928,7 +809,7 @@ __device__ __forceinline__ void pqg_walk(const p_u32x4 *__restrict__ A, const p_
     constexpr int CARRY = S + G < 63 ? S + G : 63;
     const int N_ = N;
     static_assert(EPI == 1 || EPI == 2, "bias + ReLU, heads optional");
-    __shared__ p_u32x4 lds[3 * STG];
+    __shared__ u32x4 lds[3 * STG];
     __shared__ int32_t gmap[2 * XS];
 
     int v = blockIdx.x;
@@ -937,7 +818,7 @@ __device__ __forceinline__ void pqg_walk(const p_u32x4 *__restrict__ A, const p_
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int wm = w / WGN, wn = w - (w / WGN) * WGN;
     const int fr = lane & 31, fh = lane >> 5;
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) p_u32x4 *)lds;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) u32x4 *)lds;
     const uint32_t gm0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int32_t *)gmap;
     const uint32_t wbase = (uint32_t)__builtin_amdgcn_readfirstlane(w) * 64u;
 
@@ -973,12 +854,12 @@ __device__ __forceinline__ void pqg_walk(const p_u32x4 *__restrict__ A, const p_
     for (int i = 0; i < GA; i++) {
         const int q = i * NT + tid, r = q >> 3;
         ga[i] = r * KC;
-        ca[i] = (uint32_t)((q & 7) ^ p_swz(r)) * 16u;
+        ca[i] = (uint32_t)((q & 7) ^ g_swz(r)) * 16u;
     }
 #pragma unroll
     for (int i = 0; i < GB; i++) {
         const int q = i * NT + tid, r = q >> 3;
-        offB[i] = (uint32_t)(r * (K / 4) + ((q & 7) ^ p_swz(r))) * 16u;
+        offB[i] = (uint32_t)(r * (K / 4) + ((q & 7) ^ g_swz(r))) * 16u;
     }
     // (every DMA source is a uniform base + a 32-bit byte offset per lane: the launcher refuses operands past 4 GB)
     // the row map of the tile at m0 into buffer bf (rows past M - 1 clamped: read, never stored; the entries past
@@ -1001,7 +882,7 @@ __device__ __forceinline__ void pqg_walk(const p_u32x4 *__restrict__ A, const p_
             g[i] = (uint32_t)*(const lds_i32 *)(uintptr_t)(gm0 + (uint32_t)(bf * XS + ga[i] + kt / 2) * 4u) * 256u +
                    ca[i];
     };
-    const p_u32x4 *At, *baseB;  // of the item the DMAs are issued for
+    const u32x4 *At, *baseB;  // of the item the DMAs are issued for
     auto set_base = [&](const PItem &it) __attribute__((always_inline)) {
         At = A + it.t * sA;
         baseB = B + it.t * sB + (int64_t)it.n0 * (K / 4);
@@ -1028,7 +909,7 @@ __device__ __forceinline__ void pqg_walk(const p_u32x4 *__restrict__ A, const p_
         asm volatile("" : "+s"(N), "+v"(rw), "+v"(rp));
         if constexpr (EPI == 2) {
             float *part = hpart + ((int64_t)(cur.t * tiles_n + cur.tn) * WGN + wn) * M * 4;
-            c.store_heads(FULL, Ct, part, N, M, cur.m0, rw, rp, col0, fr, inv, invB, bvv, wv);
+            c.store_heads(FULL, IC<2>{}, Ct, part, N, M, cur.m0, rw, rp, col0, fr, inv, invB, bvv, wv);
         } else {
             c.store(FULL, IC<1>{}, Ct, N, M, cur.m0, rw, col0, inv, invB, bvv);
         }
@@ -1103,7 +984,7 @@ __device__ __forceinline__ void pqg_walk(const p_u32x4 *__restrict__ A, const p_
 // x column tiles of one tower; the one-tile form's grid is (tiles, T), the walk's at most one block per CU
 template <int BM, int BN, int WGM, int WGN, int EPI, int NK, int NS = 3, bool ONE = false, int ORD = 0,
           bool PERS = false>
-__global__ __launch_bounds__(64 * WGM * WGN) void k_h3_pq(const p_u32x4 *__restrict__ A, const p_u32x4 *__restrict__ B,
+__global__ __launch_bounds__(64 * WGM * WGN) void k_h3_pq(const u32x4 *__restrict__ A, const u32x4 *__restrict__ B,
                                                           const uint32_t *__restrict__ amaxA,
                                                           const uint32_t *__restrict__ amaxB, int64_t M, int N, int K,
                                                           int64_t sA, int64_t sB, const float *__restrict__ bias,
@@ -1118,7 +999,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_h3_pq(const p_u32x4 *__restr
 }
 
 template <int BM, int BN, int WGM, int WGN, int EPI, bool PERS = false>
-__global__ __launch_bounds__(64 * WGM * WGN) void k_h3_pqg(const p_u32x4 *__restrict__ A, const p_u32x4 *__restrict__ B,
+__global__ __launch_bounds__(64 * WGM * WGN) void k_h3_pqg(const u32x4 *__restrict__ A, const u32x4 *__restrict__ B,
                                                            const uint32_t *__restrict__ amaxA,
                                                            const uint32_t *__restrict__ amaxB, int64_t M, int N,
                                                            int64_t sA, int64_t sB, const float *__restrict__ bias,
@@ -1177,8 +1058,8 @@ hipError_t pq_launch(const void *A, const void *B, const uint32_t *amaxA, const 
     PGrid g;
     if (pq_grid(M, N, T, BM, BN, PERS, g) != hipSuccess) return hipErrorInvalidValue;
     const dim3 block(64 * WGM * WGN);
-    const auto *a = static_cast<const p_u32x4 *>(A);
-    const auto *b = static_cast<const p_u32x4 *>(B);
+    const auto *a = static_cast<const u32x4 *>(A);
+    const auto *b = static_cast<const u32x4 *>(B);
 #define PQ_K(NK)                                                                                                    \
     do {                                                                                                            \
         if (bias)                                                                                                   \
@@ -1224,8 +1105,8 @@ hipError_t launch_h3p_gemm_nt(const void *A, const uint32_t *amaxA, const void *
         PGrid g;
         if (pq_grid(M, N, T, BM, BN, walk, g) != hipSuccess) return hipErrorInvalidValue;
         const dim3 block(512);
-        const auto *a = static_cast<const p_u32x4 *>(A);
-        const auto *b = static_cast<const p_u32x4 *>(B);
+        const auto *a = static_cast<const u32x4 *>(A);
+        const auto *b = static_cast<const u32x4 *>(B);
 #define PQG(EPI, PERS, ...)                                                                                          \
     hipLaunchKernelGGL((k_h3_pqg<BM, BN, 2, 4, EPI, PERS>), g.grid, block, 0, s, a, b, amaxA, amaxB, M, N,           \
                        a_stride / 4, b_stride / 4, bias, C, c_stride, g.tiles_n, g.tiles, g.W, a_rows, __VA_ARGS__)
@@ -1284,11 +1165,11 @@ hipError_t launch_h3p_gemm_tn_gather(const void *A, const uint32_t *amaxA, const
     *S_out = S;
     if (cfg == 21)
         hipLaunchKernelGGL((k_h3_tq<64, BN, 2, 2>), dim3(tiles * S * T), dim3(256), 0, s,
-                           static_cast<const p_u32x4 *>(A), static_cast<const p_u32x4 *>(B), amaxA, amaxB, Kd, M, N,
+                           static_cast<const u32x4 *>(A), static_cast<const u32x4 *>(B), amaxA, amaxB, Kd, M, N,
                            a_stride / 4, b_stride / 4, kc, tiles_n, tiles, S, slab, b_rows);
     else
         hipLaunchKernelGGL((k_h3_tq<128, BN, 4, 2>), dim3(tiles * S * T), dim3(512), 0, s,
-                           static_cast<const p_u32x4 *>(A), static_cast<const p_u32x4 *>(B), amaxA, amaxB, Kd, M, N,
+                           static_cast<const u32x4 *>(A), static_cast<const u32x4 *>(B), amaxA, amaxB, Kd, M, N,
                            a_stride / 4, b_stride / 4, kc, tiles_n, tiles, S, slab, b_rows);
     return hipGetLastError();
 }

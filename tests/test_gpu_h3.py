@@ -112,6 +112,65 @@ def test_gemm_tn_vs_float64(device, Kd, splits, scale, cfg):
     assert torch.equal(Wq, W)
 
 
+# The window GEMMs' instantiations (merlin/windows.py: the forward on NT cfg 11 at K = 64, the input gradient on NT
+# cfg 5, the weight gradient on TN cfg 2), held as the fc1 shapes above are: against float64 under torch's own fp32
+# error on the same operands, and to the bits of another path that sums the same products in the same order.
+@pytest.mark.parametrize("M", [1, 777])
+def test_gemm_nt_window_dgrad_cfg5(device, M):
+    """k_h3_nt<128, 64, 4, 1>: one column tile of 64."""
+    from merlin import _native as nat
+
+    N, K = 64, 576
+    A, B = _operands(device, M, N, K, M + 5)
+    bias = torch.randn(2, N, device=device)
+    C64 = torch.bmm(A.double(), B.double().transpose(1, 2))
+    den = torch.bmm(A.abs().double(), B.abs().double().transpose(1, 2))
+    tol = max(_err(torch.bmm(A, B.transpose(1, 2)), C64, den), FLOOR)
+    amA, amB = nat.h3_amax(A), nat.h3_amax(B)
+    Bp = nat.h3_split(B, amB)
+    C = nat.h3_gemm_nt(A, amA, Bp, amB, cfg=5)
+    assert _err(C, C64, den) <= tol
+    assert torch.equal(C, nat.h3_gemm_nt(A, amA, Bp, amB, cfg=5))
+    Cb = nat.h3_gemm_nt(A, amA, Bp, amB, bias=bias, cfg=5)
+    assert torch.equal(Cb, torch.relu(C + bias.unsqueeze(1)))
+    assert torch.equal(Cb, nat.h3_gemm_nt(A, amA, Bp, amB, bias=bias, cfg=5))
+
+
+@pytest.mark.parametrize("M", [1, 777])
+def test_gemm_nt_window_fwd_cfg11_two_steps(device, M):
+    """k_h3_ntp<128, 192, 4, 2> at K = 64: nk = 2, the peeled loop with an empty main loop."""
+    from merlin import _native as nat
+
+    N, K = 576, 64
+    A, B = _operands(device, M, N, K, M + 11)
+    C64 = torch.bmm(A.double(), B.double().transpose(1, 2))
+    den = torch.bmm(A.abs().double(), B.abs().double().transpose(1, 2))
+    tol = max(_err(torch.bmm(A, B.transpose(1, 2)), C64, den), FLOOR)
+    amA, amB = nat.h3_amax(A), nat.h3_amax(B)
+    Bp = nat.h3_split(B, amB)
+    C = nat.h3_gemm_nt(A, amA, Bp, amB, cfg=11)
+    assert _err(C, C64, den) <= tol
+    assert torch.equal(C, nat.h3_gemm_nt(A, amA, Bp, amB, cfg=1))
+
+
+@pytest.mark.parametrize("Kd,splits", [(1, 1), (257, 1), (4093, 7)])
+def test_gemm_tn_window_wgrad_cfg2(device, Kd, splits):
+    """k_h3_tn<64, 192, 2, 2> (M = 64), and k_h3_tnq<64, 192, 2, 2> over both operands' planes: the same bits."""
+    from merlin import _native as nat
+
+    g = torch.Generator(device=device).manual_seed(Kd + 2)
+    dz = torch.randn(2, Kd, 64, device=device, generator=g) * (torch.rand(2, Kd, 64, device=device, generator=g) > 0.5)
+    a3 = torch.relu(torch.randn(2, Kd, 576, device=device, generator=g))
+    W64 = torch.bmm(dz.double().transpose(1, 2), a3.double())
+    den = torch.bmm(dz.abs().double().transpose(1, 2), a3.abs().double())
+    tol = max(_err(torch.bmm(dz.transpose(1, 2), a3), W64, den), FLOOR)
+    amz, am3 = nat.h3_amax(dz), nat.h3_amax(a3)
+    W = nat.h3_gemm_tn(dz, amz, a3, am3, splits=splits, cfg=2)
+    assert _err(W, W64, den) <= tol
+    Wq = nat.h3_gemm_tn(nat.h3_split(dz, amz), amz, nat.h3_split(a3, am3), am3, splits=splits, cfg=2)
+    assert torch.equal(Wq, W)
+
+
 @pytest.mark.parametrize("cfg", [0, 1])
 def test_gemm_tn_cancellation(device, cfg):
     """The update's weight gradient: ~1e5 rows whose terms nearly cancel (|W| ~ 1e-2 sum |a b|)."""
