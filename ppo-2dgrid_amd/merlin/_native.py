@@ -1606,7 +1606,8 @@ def clip_adam(params, grads, exp_avgs, exp_avg_sqs, steps, lr, beta1, beta2, eps
               workspace=None):
     """clip_grad_norm_(params, max_norm) + torch's fused Adam step (src/ppo.py:153-156) in two
     launches (merlin_clip_adam): the gradients are clipped in place, (param, exp_avg, exp_avg_sq)
-    updated, each float32[1] step counter advanced.  Returns the pre-clip global norm (norm_out)."""
+    updated, each float32[1] step counter advanced (a zero-element tensor's too, as torch's Adam does).  Returns
+    the pre-clip global norm (norm_out)."""
     n = len(params)
     if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(steps) == n):
         raise ValueError("clip_adam: parameter / state lists differ in length")
@@ -1617,6 +1618,21 @@ def clip_adam(params, grads, exp_avgs, exp_avg_sqs, steps, lr, beta1, beta2, eps
     for p, g, m, v in zip(params, grads, exp_avgs, exp_avg_sqs):
         if not (p.numel() == g.numel() == m.numel() == v.numel()):
             raise ValueError("clip_adam: a parameter and its gradient / state differ in size")
+    if n > 32:
+        raise ValueError("clip_adam: at most 32 tensors")
+    if any(p.numel() == 0 for p in params):
+        # a tensor without elements adds nothing to the norm and has nothing to update, but torch's Adam still
+        # advances its step counter; merlin_clip_adam takes numel > 0 only, so it gets the other tensors
+        for p, st in zip(params, steps):
+            if p.numel() == 0:
+                st += 1
+        keep = [i for i, p in enumerate(params) if p.numel() > 0]
+        if not keep:
+            dev = params[0].device
+            return torch.zeros((), dtype=torch.float32, device=dev) if norm_out is None else norm_out.zero_()
+        params, grads, exp_avgs, exp_avg_sqs, steps = ([ts[i] for i in keep]
+                                                       for ts in (params, grads, exp_avgs, exp_avg_sqs, steps))
+        n = len(keep)
     numel = (C.c_int64 * n)(*[int(p.numel()) for p in params])
     arr = lambda ts: (C.c_void_p * n)(*[ptr(t).value for t in ts])  # noqa: E731
     dev = params[0].device

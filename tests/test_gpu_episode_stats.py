@@ -109,3 +109,28 @@ def test_classes_beyond_n_classes_are_ignored(device):
     done, ret, length, cls = synth(5, 200, 5, seed=4)
     ref = host_stats(done, ret, length, cls, 3)
     check(run(device, done, ret, length, cls, 3), ref)
+
+
+def test_more_column_tiles_than_one_round(device):
+    """T = 2, N = 256 * 1024 + 257: 1,026 column tiles against a workspace of 1,024 block partials, so two rounds
+    (1,024 tiles, then 2 with the last holding one env), the second folded onto the first; one step slab each."""
+    T, N, n_classes = 2, 256 * 1024 + 257, 5
+    assert -(-N // 256) == 1024 + 2 and N % 256 == 1
+    done, ret, length, cls = synth(T, N, n_classes, seed=11)
+    done[:, -1], cls[-1] = 1.0, 2  # the env alone in the last tile finishes, twice
+    ref = host_stats(done, ret, length, cls, n_classes)
+    assert all(r[0] > 0 for r in ref)
+    late = host_stats(done[:, 256 * 1024:], ret[:, 256 * 1024:], length[:, 256 * 1024:], cls[256 * 1024:], n_classes)
+    assert all(r[0] > 0 for r in late)  # every class has episodes in the second round
+    a = run(device, done, ret, length, cls, n_classes)
+    check(a, ref)
+    b = run(device, done, ret, length, cls, n_classes)
+    assert torch.equal(a.view(torch.int64), b.view(torch.int64))
+    # into a prefilled `out`: the first round overwrites, the second adds; accumulate adds both
+    c = run(device, done, ret, length, cls, n_classes, out=torch.full((n_classes, 4), 7.0, dtype=torch.float64,
+                                                                       device=device))
+    assert torch.equal(a.view(torch.int64), c.view(torch.int64))
+    acc = a.clone()
+    run(device, done, ret, length, cls, n_classes, out=acc, accumulate=True)
+    assert torch.equal(acc[:, 0], 2 * a[:, 0]) and torch.equal(acc[:, 3], 2 * a[:, 3])
+    check(acc, [(2 * cnt, 2 * s1, 2 * s2, 2 * sl, 2 * a1, 2 * a2) for cnt, s1, s2, sl, a1, a2 in ref])

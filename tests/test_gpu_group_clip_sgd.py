@@ -122,3 +122,73 @@ def test_argument_checks(device):
     with pytest.raises(nat.MerlinNativeError):
         nat.group_clip_sgd([p], [p.double()], LR, MAX_NORM)
     assert nat.group_clip_sgd([p[:0]], [p[:0]], LR, MAX_NORM).numel() == 0  # G = 0
+
+
+EDGE_NUMEL = [1, 1023, 1024, 1025, 2049, 4096]  # around the 1,024-element chunk
+
+
+def _edge_case(G_, shapes, seed):
+    """Task 0 (and 2): gradient norm about 50, clipped; task 1: about 0.3, coefficient 1."""
+    rs = np.random.RandomState(seed)
+    params = [rs.randn(G_, *s).astype(np.float32) for s in shapes]
+    grads = [rs.randn(G_, *s).astype(np.float32) for s in shapes]
+    n_all = sum(int(np.prod(s)) for s in shapes)
+    for g in grads:
+        g[0::2] *= np.float32(50.0 / np.sqrt(n_all))
+        g[1::2] *= np.float32(0.3 / np.sqrt(n_all))
+    return params, grads
+
+
+def _check_restatement(params, grads, p1, g1, norm, G_):
+    for t in range(G_):
+        ref_norm, ref_g, ref_p = _restate(params, grads, t)
+        assert (40 < ref_norm < 60) if t % 2 == 0 else ref_norm < MAX_NORM
+        assert abs(norm[t] - ref_norm) <= 1e-6 * ref_norm, (t, norm[t], ref_norm)
+        for i in range(len(params)):
+            eg = np.abs(g1[i][t] - ref_g[i])
+            ep = np.abs(p1[i][t] - ref_p[i])
+            assert (eg <= 4 * EPS * np.abs(ref_g[i])).all(), (t, i)
+            assert (ep <= 4 * EPS * (np.abs(params[i][t]) + LR * np.abs(grads[i][t]))).all(), (t, i)
+
+
+@pytest.mark.parametrize("G_", [1, 3])
+def test_chunk_edges_match_float64_restatement(device, G_):
+    """Per task, tensors one element long, one short of a chunk, a chunk, one over, two chunks and one, four chunks."""
+    params, grads = _edge_case(G_, [(k,) for k in EDGE_NUMEL], 20 + G_)
+    p1, g1, norm = _run(device, params, grads)
+    _check_restatement(params, grads, p1, g1, norm, G_)
+
+
+def test_32_tensors_and_no_more(device):
+    """32 tensors (OPT_MAX_TENSORS) work; 33 are refused with nothing written."""
+    from merlin import _native as nat
+
+    shapes = [(EDGE_NUMEL[i % len(EDGE_NUMEL)] + i // len(EDGE_NUMEL),) for i in range(32)]
+    params, grads = _edge_case(2, shapes, 30)
+    p1, g1, norm = _run(device, params, grads)
+    _check_restatement(params, grads, p1, g1, norm, 2)
+
+    p = [torch.from_numpy(x.copy()).to(device) for x in params] + [torch.ones(2, 7, device=device)]
+    g = [torch.from_numpy(x.copy()).to(device) for x in grads] + [torch.ones(2, 7, device=device)]
+    norm_out = torch.full((2,), -3.0, device=device)
+    with pytest.raises(ValueError):
+        nat.group_clip_sgd(p, g, LR, MAX_NORM, norm_out=norm_out)
+    torch.cuda.synchronize()
+    for a, b in zip(p + g, params + [np.ones((2, 7), np.float32)] + grads + [np.ones((2, 7), np.float32)]):
+        assert (a.cpu().numpy().view(np.int32) == b.view(np.int32)).all()
+    assert (norm_out == -3.0).all()
+
+
+def test_empty_tensor_is_refused(device):
+    """A tensor without elements per task is refused, in any position, with nothing written."""
+    from merlin import _native as nat
+
+    for pos in (0, 1, 2):
+        p = [torch.ones(3, 5, device=device), torch.ones(3, 1025, device=device)]
+        p.insert(pos, torch.ones(3, 0, device=device))
+        g = [torch.full_like(x, 2.0) for x in p]
+        norm_out = torch.full((3,), -3.0, device=device)
+        with pytest.raises(ValueError):
+            nat.group_clip_sgd(p, g, LR, MAX_NORM, norm_out=norm_out)
+        torch.cuda.synchronize()
+        assert all((x == 1.0).all() for x in p) and all((x == 2.0).all() for x in g) and (norm_out == -3.0).all()

@@ -141,3 +141,109 @@ def test_adv_normalisation_vs_reference(golden, device):
         a = torch.from_numpy(g[f"c{k}_adv"]).to(device)
         norm = nat.adv_normalize(a, stats).cpu().numpy()
         np.testing.assert_allclose(norm, g[f"c{k}_advnorm"], rtol=1e-5, atol=1e-5)
+
+
+def _gae_case(T, N, seed):
+    """Rewards / values / bootstrap of tests/test_gpu_obs_gae.py's shape test, and the done patterns that put an
+    episode end on every seam of the two kernels: the wave kernel cuts T into 64 chunks of L = ceil(T / 64) steps
+    (lane k owns t = kL .. kL + L - 1), the thread kernel walks t = T - 2 .. 0 in load batches of 8 and a tail."""
+    rs = np.random.RandomState(seed)
+    r = ((rs.rand(T, N) < 0.05) * rs.rand(T, N)).astype(np.float32)
+    v = rs.randn(T, N).astype(np.float32)
+    lv = rs.randn(N).astype(np.float32)
+    L = -(-T // 64)
+    z = np.zeros((T, N), dtype=np.float32)
+    pats = {"none": z, "all": z + 1, "last": z.copy(), "first": z.copy(), "chunk_edges": z.copy(),
+            "batch_edges": z.copy(), "random": (rs.rand(T, N) < 0.02).astype(np.float32)}
+    pats["last"][T - 1] = 1
+    pats["first"][0] = 1
+    pats["chunk_edges"][::L] = 1          # t = kL: the first step of every chunk
+    pats["chunk_edges"][L - 1::L] = 1     # t = kL - 1: the last step of the chunk before
+    for t in range(T - 1):                # the first and the last step of every load batch of the thread kernel
+        if (T - 2 - t) % 8 in (0, 7):
+            pats["batch_edges"][t] = 1
+    return r, v, lv, pats
+
+
+def _gae_prefilled(device, r, v, d, lv, gamma):
+    """nat.gae into adv / ret prefilled with NaN, with stats: (adv, ret, stats) on the host."""
+    from merlin import _native as nat
+
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(device)  # noqa: E731
+    adv = torch.full(r.shape, float("nan"), dtype=torch.float32, device=device)
+    ret = torch.full(r.shape, float("nan"), dtype=torch.float32, device=device)
+    stats = torch.full((3,), float("nan"), dtype=torch.float64, device=device)
+    nat.gae(t(r), t(v), t(d), t(lv), gamma, 0.95, adv=adv, ret=ret, stats=stats)
+    return adv.cpu().numpy(), ret.cpu().numpy(), stats.cpu().numpy()
+
+
+def _check_gae_stats(s, adv, T, N):
+    # as test_gae_and_normalisation_shapes: the count exact, the moments the f64 sums of the kernel's own advantages
+    assert s[0] == T * N
+    np.testing.assert_allclose(s[1], adv.astype(np.float64).sum(), rtol=1e-12, atol=1e-9)
+    np.testing.assert_allclose(s[2], (adv.astype(np.float64) ** 2).sum(), rtol=1e-12)
+
+
+@pytest.mark.parametrize("T", [1, 2, 8, 9, 10, 16, 17, 31])
+@pytest.mark.parametrize("N", [257, 300])
+def test_gae_thread_kernel_ragged_T(oracle, device, N, T):
+    """N > 256, the thread-per-env kernel: the step T - 1 alone (T = 1), no load batch (T - 1 < 8), exactly one
+    (T = 9), one and a tail (10, 16), two and no tail (17), three and a tail (31); a second block with 1 / 44 live
+    threads.  Bit-exact with the reference's op order, every element written."""
+    r, v, lv, pats = _gae_case(T, N, 100 * N + T)
+    for name, d in pats.items():
+        adv, ret, s = _gae_prefilled(device, r, v, d, lv, 0.99)
+        assert np.isfinite(adv).all() and np.isfinite(ret).all(), name
+        oadv, oret = oracle.gae_tn(r, v, d, lv)
+        assert (adv == oadv).all() and (ret == oret).all(), name
+        _check_gae_stats(s, adv, T, N)
+
+
+@pytest.mark.parametrize("T", [1, 2, 5, 63, 64, 65, 100, 127, 129, 300])
+@pytest.mark.parametrize("N", [1, 3, 256])
+def test_gae_wave_kernel_ragged_T(oracle, device, N, T):
+    """N <= 256, one wave per env, the horizons merlin/evaluation.py and merlin/fomaml.py pass: T < 64 leaves lanes
+    empty (L = 1), T = 65 .. 127 gives chunks of 2 with the last lanes empty and one part-filled (65, 127), 129 and
+    300 chunks of 3 and 5.  Against the oracle at this file's 1e-5, both gammas, every element written."""
+    r, v, lv, pats = _gae_case(T, N, 100 * N + T)
+    for gamma in (0.99, 0.995):
+        for name, d in pats.items():
+            adv, ret, s = _gae_prefilled(device, r, v, d, lv, gamma)
+            assert np.isfinite(adv).all() and np.isfinite(ret).all(), (name, gamma)
+            oadv, oret = oracle.gae_tn(r, v, d, lv, gamma=gamma)
+            np.testing.assert_allclose(adv, oadv, rtol=1e-5, atol=1e-5, err_msg=f"{name} {gamma}")
+            np.testing.assert_allclose(ret, oret, rtol=1e-5, atol=1e-5, err_msg=f"{name} {gamma}")
+            _check_gae_stats(s, adv, T, N)
+
+
+@pytest.mark.parametrize("n", [2 ** 20 + 1, 3 * 2 ** 20 + 5])
+def test_adv_normalisation_beyond_the_grid_cap(oracle, device, n):
+    """More than 4,096 blocks of 256 elements: the grid-stride loop takes a second (2^20 + 1: for one thread only)
+    and a fourth turn.  stats are the host's float64 sums."""
+    from merlin import _native as nat
+
+    a = np.random.RandomState(n % 1000).randn(n).astype(np.float32)
+    a64 = a.astype(np.float64)
+    stats = torch.tensor([float(n), a64.sum(), (a64 * a64).sum()], dtype=torch.float64, device=device)
+    out = torch.full((n,), float("nan"), dtype=torch.float32, device=device)
+    nat.adv_normalize(torch.from_numpy(a).to(device), stats, out=out)
+    np.testing.assert_allclose(out.cpu().numpy(), oracle.adv_normalize(a), rtol=1e-5, atol=1e-5)
+
+
+def test_adv_normalisation_of_a_constant_is_exact_zero(device):
+    """A constant c: the exact sums give a variance of exactly 0; a sum of squares one unit in the last place low
+    (what a rounded summation can return) gives a slightly negative one, which the kernel clamps.  Both normalise
+    to exact zeros -- (c - c) / 1e-8 -- where an unclamped square root would give NaN."""
+    from merlin import _native as nat
+
+    n = 2 ** 20 + 1
+    c = np.float32(0.3)
+    s1, s2 = float(n) * float(c), float(n) * (float(c) * float(c))  # n c exact (46 bits), n c^2 rounded once
+    a = torch.full((n,), float(c), dtype=torch.float32, device=device)
+    for sq in (s2, float(np.nextafter(s2, 0.0))):
+        mean = s1 / n
+        var = (sq - s1 * mean) / (n - 1.0)  # k_adv_normalize's float64 expression
+        assert mean == float(c) and (var < 0.0 if sq != s2 else var == 0.0)
+        stats = torch.tensor([float(n), s1, sq], dtype=torch.float64, device=device)
+        out = nat.adv_normalize(a, stats)
+        assert (out == 0).all()
