@@ -20,7 +20,6 @@ namespace {
 constexpr int EBLK = 256;
 constexpr int MAXA = 8;  // act_dim limit of the fused head backward
 
-__device__ __forceinline__ float relu_nan(float v) { return v != v ? v : fmaxf(v, 0.0f); }  // torch.relu keeps NaN
 __device__ __forceinline__ float4 f4_zero() { return make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
 __device__ __forceinline__ void f4_add(float4 &a, const float4 b) {
     a.x += b.x;

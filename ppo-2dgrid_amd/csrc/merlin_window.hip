@@ -34,7 +34,6 @@ __device__ __forceinline__ void f4_add(float4 &a, const float4 b) {
     a.z += b.z;
     a.w += b.w;
 }
-__device__ __forceinline__ float relu_nan(float v) { return v != v ? v : fmaxf(v, 0.0f); }  // torch.relu keeps NaN
 // ReLU backward (threshold_backward): g where y > 0, else 0
 __device__ __forceinline__ float4 f4_mask(const float4 y, const float4 g) {
     return make_float4(y.x > 0.0f ? g.x : 0.0f, y.y > 0.0f ? g.y : 0.0f, y.z > 0.0f ? g.z : 0.0f,

@@ -7,6 +7,8 @@ own fp32 GEMM (hipBLASLt) on the same operands, measured as max |C - C64| / sum_
 gradient (the update's: the result ~1e-2 of sum |a b|) the error relative to the result's norm must
 not exceed hipBLASLt's own split-K product's.  Shapes: the update's fc1 (K = 576 / 512, N = 512 /
 576) at row counts that are not tile multiples, both towers with their own operands."""
+import functools
+
 import pytest
 import torch
 
@@ -37,9 +39,12 @@ def test_split_is_exact(device):
     assert torch.equal(p0.view(torch.bfloat16), x.to(torch.bfloat16))
 
 
-@pytest.mark.parametrize("N,K,cfg", [(512, 576, 0), (576, 512, 1), (512, 576, 2), (576, 512, 3), (512, 576, 20),
-                                     (576, 512, 22), (512, 576, 21), (576, 512, 23), (512, 576, 26),
-                                     (576, 512, 27), (512, 576, 28), (512, 576, 24), (512, 576, 25)])
+NT_CASES = [(512, 576, 0), (576, 512, 1), (512, 576, 2), (576, 512, 3), (512, 576, 20), (576, 512, 22), (512, 576, 21),
+            (576, 512, 23), (512, 576, 26), (576, 512, 27), (512, 576, 28), (512, 576, 24), (512, 576, 25)]
+TN_CFGS = [0, 1, 2, 20, 21, 24, 25]
+
+
+@pytest.mark.parametrize("N,K,cfg", NT_CASES)
 @pytest.mark.parametrize("M", [1, 777, 20011])
 def test_gemm_nt_vs_float64(device, M, N, K, cfg):
     from merlin import _native as nat
@@ -58,7 +63,7 @@ def test_gemm_nt_vs_float64(device, M, N, K, cfg):
     assert torch.equal(Cb, torch.relu(C + bias.unsqueeze(1)))
 
 
-@pytest.mark.parametrize("cfg", [0, 1, 2, 20, 21, 24, 25])
+@pytest.mark.parametrize("cfg", TN_CFGS)
 @pytest.mark.parametrize("Kd,splits", [(1, 1), (4093, 7), (40000, 32), (40000, 64)])
 def test_gemm_tn_vs_float64(device, Kd, splits, cfg):
     from merlin import _native as nat
@@ -74,6 +79,70 @@ def test_gemm_tn_vs_float64(device, Kd, splits, cfg):
     assert _err(W, W64, den) <= tol
     # fixed-order slab fold: bitwise reproducible
     assert torch.equal(W, nat.x6_gemm_tn(dz, a3, splits=splits, cfg=cfg))
+
+
+@functools.lru_cache(maxsize=None)
+def _nt_edge_operands(M, K):
+    """Two towers' operands at N = 384 with their float64 product, shared by every cfg of test_gemm_nt_edges."""
+    from merlin import _native as nat
+
+    dev = torch.device("cuda")
+    g = torch.Generator(device=dev).manual_seed(1000 * K + M)
+    A = torch.relu(torch.randn(2, M, K, device=dev, generator=g))
+    B = torch.randn(2, 384, K, device=dev, generator=g) / K ** 0.5
+    bias = torch.randn(2, 384, device=dev, generator=g)
+    C64 = torch.bmm(A.double(), B.double().transpose(1, 2))
+    den = torch.bmm(A.abs().double(), B.abs().double().transpose(1, 2))
+    tol = max(2 * _err(torch.bmm(A, B.transpose(1, 2)), C64, den), TOL_FLOOR)
+    return A, nat.x6_split(B), bias, C64, den, tol
+
+
+@pytest.mark.parametrize("cfg", [c for _, _, c in NT_CASES])
+@pytest.mark.parametrize("K", [32, 64, 96])
+@pytest.mark.parametrize("M", [1, 127, 129, 257])
+def test_gemm_nt_edges(device, M, K, cfg):
+    """The staging pipeline's short ends and the row edges: K = 32 is the 32-deep bodies' prologue alone, 64 the first
+    shape with no load two steps ahead, 96 the first full rotation; M on either side of a 128- and a 256-row tile
+    edge (the clamped row reads, the row < M guard).  N = 384 is a multiple of every BN in use (64, 128, 192)."""
+    from merlin import _native as nat
+
+    A, Bp, bias, C64, den, tol = _nt_edge_operands(M, K)
+    C = nat.x6_gemm_nt(A, Bp, cfg=cfg)
+    print(f"nt edges M={M} K={K} cfg={cfg}: err {_err(C, C64, den):.3e} tol {tol:.3e}")
+    assert _err(C, C64, den) <= tol
+    Cb = nat.x6_gemm_nt(A, Bp, bias=bias, cfg=cfg)
+    assert torch.equal(Cb, torch.relu(C + bias.unsqueeze(1)))
+
+
+@functools.lru_cache(maxsize=None)
+def _tn_edge_operands(Kd):
+    """Two towers' plain randn operands (M = 256, N = 192: one to six tiles for every tile shape in use) with their
+    float64 product, shared by every cfg of test_gemm_tn_edges."""
+    dev = torch.device("cuda")
+    g = torch.Generator(device=dev).manual_seed(7000 + Kd)
+    A = torch.randn(2, Kd, 256, device=dev, generator=g)
+    B = torch.randn(2, Kd, 192, device=dev, generator=g)
+    W64 = torch.bmm(A.double().transpose(1, 2), B.double())
+    den = torch.bmm(A.abs().double().transpose(1, 2), B.abs().double())
+    tol = max(2 * _err(torch.bmm(A.transpose(1, 2), B), W64, den), TOL_FLOOR)
+    return A, B, W64, den, tol
+
+
+@pytest.mark.parametrize("cfg", TN_CFGS)
+@pytest.mark.parametrize("Kd,splits", [(1, 1), (15, 1), (16, 1), (17, 1), (31, 1), (32, 1), (33, 2), (64, 2), (65, 3),
+                                       (33, 64)])
+def test_gemm_tn_edges(device, Kd, splits, cfg):
+    """The ends of a split's k range: a lone ragged step, exactly one step of either depth (16, 32), one full step
+    plus a ragged one, a second split holding a single row, more splits asked than the rows can fill.  The operands
+    are plain randn, not masked and not ReLU'd, so a row leaked from past a split's end (the next split's, or the other
+    tower's) is an O(1) error, far above the tolerance."""
+    from merlin import _native as nat
+
+    A, B, W64, den, tol = _tn_edge_operands(Kd)
+    W = nat.x6_gemm_tn(A, B, splits=splits, cfg=cfg)
+    print(f"tn edges Kd={Kd} splits={splits} cfg={cfg}: err {_err(W, W64, den):.3e} tol {tol:.3e}")
+    assert _err(W, W64, den) <= tol
+    assert torch.equal(W, nat.x6_gemm_tn(A, B, splits=splits, cfg=cfg))
 
 
 @pytest.mark.parametrize("cfg", [0, 20, 21, 24, 25])
