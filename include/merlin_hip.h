@@ -102,7 +102,8 @@ extern "C" {
 #define MERLIN_DEVERR_BAD_FRAME 16u  /* a rendered frame's agent was outside the grid, on a wall or had a direction
                                       * outside 0..3, or its env id was out of range: the frame is drawn without the
                                       * agent and its highlight.  merlin_env_render: merlin_env_errors;
-                                      * merlin_render_frames: merlin_tower_errors */
+                                      * merlin_render_frames: merlin_tower_errors.  merlin_view_codes raises it there
+                                      * too, for a pose that has no view */
 
 /* observation layouts for merlin_obs_expand_f32 */
 #define MERLIN_LAYOUT_NCHW 0 /* [n][3][56][56]: what CNNActorCritic._format_obs hands the convs */
@@ -285,6 +286,36 @@ int merlin_env_optimal_steps(merlin_env *env, int32_t *dist_dev, int16_t *field_
  * CPU-side restatement of the kernel.  field nullable. */
 int merlin_shortest_paths_host(const uint32_t *walls, const int32_t *goal, const int32_t *agent, int64_t n,
                                int32_t size, int32_t *dist, int16_t *field);
+/* The policy field (no reference counterpart).  A policy that acts on the view codes alone, by the
+ * argmax, turns a map into a functional graph over its 4 size^2 poses: the two entries below are what that needs
+ * beside the policy's own forward.
+ * Stateless observation codes, in merlin_render_frames' layouts: query q < n shows map m = map_index_dev[q] (NULL: q)
+ * -- walls_dev uint32[M][size], goal_dev int32[M][2] (NULL or a position outside the grid: no goal) -- from the pose
+ * agent_dev[q] int32[4] = (x, y, dir, 0).  codes_dev uint32[n][MERLIN_OBS_WORDS]: bit for bit the words
+ * merlin_env_reset / merlin_env_step write for an env in that state (any 4-B alignment; 16 B takes wider stores).
+ * A pose outside the grid, on a wall or with dir outside 0..3 has no view: its 8 words are zero (no agent tile:
+ * merlin_tower_codes_conv3 flags such a row as MERLIN_DEVERR_BAD_TILE) and MERLIN_DEVERR_BAD_FRAME is raised
+ * (merlin_tower_errors).  size outside 5..32, negative n or a null required pointer: MERLIN_E_INVALID; n = 0 is a
+ * no-op.  map_index_dev's values are the caller's to keep inside [0, M).  One kernel, no allocation, no host sync:
+ * capturable (after the device's first library call, which allocates the error word). */
+int merlin_view_codes(const uint32_t *walls_dev, const int32_t *goal_dev, const int32_t *agent_dev,
+                      const int32_t *map_index_dev, int64_t n, int32_t size, uint32_t *codes_dev, void *stream);
+/* action_dev int8[n_maps][4][size][size], indexed [dir][y][x] as the distance field: the action each pose takes.
+ * steps_dev int16[n_maps][4][size][size]: steps(p) = the number of actions after which an episode started in pose p
+ * terminates when every pose takes its own action under the step rule above (merlin_shortest_paths), -1 if it never
+ * does: a cycle, a forward move into a wall or off the grid, a pose on a wall, an action outside {0, 1, 2}, and
+ * every pose that leads to one of those.  No horizon is applied (values are at most 4 size^2 <= 4,096; compare with
+ * max_steps).  The goal cell is an ordinary free cell for a pose standing on it, and a free pose in front of the
+ * goal whose action is forward has steps 1 whatever the pose on the goal cell does.  A goal outside the grid: -1
+ * everywhere.  With a shortest-path action at every pose, steps equals merlin_shortest_paths' field.  Any 2-B
+ * alignment of steps_dev.  size outside 5..32, negative n_maps or a null pointer: MERLIN_E_INVALID; n_maps = 0 is a
+ * no-op.  One kernel, no allocation, no host sync: capturable. */
+int merlin_policy_paths(const uint32_t *walls_dev, const int32_t *goal_dev, const int8_t *action_dev,
+                        int64_t n_maps, int32_t size, int16_t *steps_dev, void *stream);
+/* [host] merlin_policy_paths on host arrays by another algorithm, a forward walk per pose with memoisation and cycle
+ * marks in plain C++: the library's CPU-side restatement of the kernel. */
+int merlin_policy_paths_host(const uint32_t *walls, const int32_t *goal, const int8_t *action, int64_t n_maps,
+                             int32_t size, int16_t *steps);
 /* [sync] read-and-clear the device error bits and the fallback-map counter. */
 int merlin_env_errors(merlin_env *env, uint32_t *flags_host, uint32_t *fallbacks_host,
                       void *stream);

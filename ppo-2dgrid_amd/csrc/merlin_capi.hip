@@ -410,6 +410,40 @@ int merlin_shortest_paths_host(const uint32_t *walls, const int32_t *goal, const
     return MERLIN_OK;
 }
 
+int merlin_view_codes(const uint32_t *walls, const int32_t *goal, const int32_t *agent, const int32_t *map_index,
+                      int64_t n, int32_t size, uint32_t *codes, void *stream) {
+    if (size < 5 || size > 32) return fail(MERLIN_E_INVALID, "grid size must be in [5, 32]");
+    if (n < 0) return fail(MERLIN_E_INVALID, "negative query count");
+    if (n == 0) return MERLIN_OK;
+    if (!walls || !agent || !codes) return fail(MERLIN_E_INVALID, "null argument");
+    DeviceWs *ws = nullptr;
+    int rc = device_ws(&ws);
+    if (rc) return rc;
+    HIP_TRY(merlin::launch_view_codes(walls, goal, agent, map_index, n, size, codes, ws->tower_err,
+                                      (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_policy_paths(const uint32_t *walls, const int32_t *goal, const int8_t *action, int64_t n_maps,
+                        int32_t size, int16_t *steps, void *stream) {
+    if (size < 5 || size > 32) return fail(MERLIN_E_INVALID, "grid size must be in [5, 32]");
+    if (n_maps < 0) return fail(MERLIN_E_INVALID, "negative map count");
+    if (n_maps == 0) return MERLIN_OK;
+    if (!walls || !goal || !action || !steps) return fail(MERLIN_E_INVALID, "null argument");
+    HIP_TRY(merlin::launch_policy_paths(walls, goal, action, n_maps, size, steps, (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_policy_paths_host(const uint32_t *walls, const int32_t *goal, const int8_t *action, int64_t n_maps,
+                             int32_t size, int16_t *steps) {
+    if (size < 5 || size > 32) return fail(MERLIN_E_INVALID, "grid size must be in [5, 32]");
+    if (n_maps < 0) return fail(MERLIN_E_INVALID, "negative map count");
+    if (n_maps == 0) return MERLIN_OK;
+    if (!walls || !goal || !action || !steps) return fail(MERLIN_E_INVALID, "null argument");
+    merlin::policy_paths_host(walls, goal, action, n_maps, size, steps);
+    return MERLIN_OK;
+}
+
 int64_t merlin_env_config_layout(int64_t *offsets_host, int32_t n_fields) {
     const int64_t off[MERLIN_ENV_CONFIG_FIELDS] = {
         (int64_t)offsetof(merlin_env_config, num_envs),     (int64_t)offsetof(merlin_env_config, size),

@@ -325,6 +325,15 @@ hipError_t launch_shortest_paths(const uint32_t *walls, const int32_t *goal, con
 hipError_t launch_env_optimal_steps(const EnvDev &E, int32_t *dist, int16_t *field, hipStream_t s);
 void shortest_paths_host(const uint32_t *walls, const int32_t *goal, const int32_t *agent, int64_t n, int S,
                          int32_t *dist, int16_t *field);
+// the policy field (merlin_policy.hip): the observation codes uint32[n][MERLIN_OBS_WORDS] of stateless poses, and
+// the steps int16[n_maps][4][size][size] after which the policy action[n_maps][4][size][size] terminates
+hipError_t launch_view_codes(const uint32_t *walls, const int32_t *goal, const int32_t *agent,
+                             const int32_t *map_index, int64_t n, int size, uint32_t *codes, uint32_t *err,
+                             hipStream_t s);
+hipError_t launch_policy_paths(const uint32_t *walls, const int32_t *goal, const int8_t *action, int64_t n_maps,
+                               int size, int16_t *steps, hipStream_t s);
+void policy_paths_host(const uint32_t *walls, const int32_t *goal, const int8_t *action, int64_t n_maps, int S,
+                       int16_t *steps);
 hipError_t launch_obs_expand_f32(const uint32_t *codes, const int64_t *index, int64_t n, float *out,
                                  float scale, int layout, hipStream_t s);
 hipError_t launch_obs_expand_u8(const uint32_t *codes, const int64_t *index, int64_t n, uint8_t *out,

@@ -193,6 +193,9 @@ def lib():
     L.merlin_shortest_paths.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp, vp]
     L.merlin_env_optimal_steps.argtypes = [vp, vp, vp, vp]
     L.merlin_shortest_paths_host.argtypes = [vp, vp, vp, i64, i32, vp, vp]
+    L.merlin_view_codes.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp]
+    L.merlin_policy_paths.argtypes = [vp, vp, vp, i64, i32, vp, vp]
+    L.merlin_policy_paths_host.argtypes = [vp, vp, vp, i64, i32, vp]
     check_env_config_layout(L)
     _lib = L
     return L
@@ -247,6 +250,7 @@ EXPORTED_SYMBOLS = (
     "merlin_frame_atlas", "merlin_render_frames", "merlin_env_render", "merlin_env_snapshot",
     "merlin_shortest_paths", "merlin_env_optimal_steps", "merlin_shortest_paths_host",
     "merlin_h3_walk_blocks",
+    "merlin_view_codes", "merlin_policy_paths", "merlin_policy_paths_host",
 )
 
 
@@ -547,6 +551,83 @@ def shortest_paths_host(walls, goal, agent, size: int, field: bool = False):
                                                fld.ctypes.data_as(vp) if field else None),
               "merlin_shortest_paths_host")
     return (dist, fld) if field else dist
+
+
+def view_codes(walls: torch.Tensor, goal: torch.Tensor | None, agent: torch.Tensor, size: int,
+               map_index: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """int32[n, 8]: the observation codes of the poses agent[q] = (x, y, dir, 0) on map map_index[q] (int32[n]; None:
+    q, then M >= n), the words MerlinVecEnv.reset / step return for an env in that state (merlin_view_codes).  walls
+    int32[M, size] bit rows, goal int32[M, 2] or None, as MerlinVecEnv.snapshot() gives them.  A pose outside the
+    grid, on a wall or with dir outside 0..3 gets a zero row and raises DEVERR_BAD_FRAME (tower_errors).  `out`: a
+    contiguous int32 tensor of n * 8 elements."""
+    S = int(size)
+    n = int(agent.shape[0])
+    assert agent.dtype == torch.int32 and agent.shape == (n, 4) and agent.is_contiguous()
+    assert walls.dtype == torch.int32 and walls.dim() == 2 and walls.shape[1] == S and walls.is_contiguous()
+    M = int(walls.shape[0])
+    assert goal is None or (goal.dtype == torch.int32 and goal.shape == (M, 2) and goal.is_contiguous())
+    if map_index is None:
+        assert M >= n, "without map_index every query needs its own map"
+    else:
+        assert map_index.dtype == torch.int32 and map_index.shape == (n,) and map_index.is_contiguous()
+        if n and not (0 <= int(map_index.min()) and int(map_index.max()) < M):
+            raise MerlinNativeError("view_codes: map_index outside [0, M)")
+    if out is None:
+        out = torch.empty((n, OBS_WORDS), dtype=torch.int32, device=agent.device)
+    if out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != n * OBS_WORDS:
+        raise MerlinNativeError(f"view_codes: out must be a contiguous int32 tensor of {n}x{OBS_WORDS} elements")
+    with torch.cuda.device(agent.device), KernelTimer.span("k_view_codes", n * (16 + 7 * 4 + 4 * OBS_WORDS)):
+        check(lib().merlin_view_codes(ptr(walls), ptr(goal), ptr(agent), ptr(map_index), n, S, ptr(out),
+                                      stream_of(agent)), "merlin_view_codes")
+    return out.view(n, OBS_WORDS)
+
+
+def policy_paths_bytes(n_maps: int, size: int) -> int:
+    """Algorithmic bytes of k_policy_paths: the rows, goal and action bytes read, the field written twice (the -1
+    fill and the values)."""
+    return n_maps * (size * 4 + 8 + 4 * size * size * (1 + 2 * 2))
+
+
+def policy_paths(walls: torch.Tensor, goal: torch.Tensor, action: torch.Tensor, size: int,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """int16[M, 4, size, size], indexed [dir][y][x]: the number of actions after which an episode started in each
+    pose terminates when every pose takes its own action action[m, dir, y, x] (int8; 0 left, 1 right, 2 forward), -1
+    if it never does (merlin_policy_paths; include/merlin_hip.h has the definition).  walls int32[M, size], goal
+    int32[M, 2], as MerlinVecEnv.snapshot() gives them.  `out`: a contiguous int16 tensor of that many elements, any
+    alignment."""
+    S = int(size)
+    M = int(walls.shape[0])
+    assert walls.dtype == torch.int32 and walls.shape == (M, S) and walls.is_contiguous()
+    assert goal.dtype == torch.int32 and goal.shape == (M, 2) and goal.is_contiguous()
+    assert action.dtype == torch.int8 and action.shape == (M, 4, S, S) and action.is_contiguous()
+    if out is None:
+        out = torch.empty((M, 4, S, S), dtype=torch.int16, device=walls.device)
+    if out.dtype != torch.int16 or not out.is_contiguous() or out.numel() != M * 4 * S * S:
+        raise MerlinNativeError(f"policy_paths: out must be a contiguous int16 tensor of {M}x4x{S}x{S} elements")
+    with torch.cuda.device(walls.device), KernelTimer.span("k_policy_paths", policy_paths_bytes(M, S)):
+        check(lib().merlin_policy_paths(ptr(walls), ptr(goal), ptr(action), M, S, ptr(out), stream_of(walls)),
+              "merlin_policy_paths")
+    return out.view(M, 4, S, S)
+
+
+def policy_paths_host(walls, goal, action, size: int):
+    """policy_paths on numpy arrays, solved on the CPU by the library's forward walk (merlin_policy_paths_host): walls
+    uint32 / int32 [M, size], goal int32[M, 2], action int8[M, 4, size, size] -> int16[M, 4, size, size]."""
+    import numpy as np
+
+    S = int(size)
+    walls = np.ascontiguousarray(np.asarray(walls).astype(np.uint32, copy=False))
+    M = int(walls.shape[0])
+    goal = np.ascontiguousarray(goal, dtype=np.int32)
+    action = np.ascontiguousarray(action, dtype=np.int8)
+    assert walls.shape == (M, S) and goal.shape == (M, 2) and action.shape == (M, 4, S, S)
+    steps = np.empty((M, 4, max(S, 0), max(S, 0)), dtype=np.int16)
+    vp = C.c_void_p
+    with KernelTimer.span("policy_paths_host", policy_paths_bytes(M, S)):
+        check(lib().merlin_policy_paths_host(walls.ctypes.data_as(vp), goal.ctypes.data_as(vp),
+                                             action.ctypes.data_as(vp), M, S, steps.ctypes.data_as(vp)),
+              "merlin_policy_paths_host")
+    return steps
 
 
 # ---------------------------------------------------------------------------
@@ -950,7 +1031,7 @@ def tower_errors(device=None, raise_on_error: bool = True) -> int:
                                 "it elsewhere -- not an observation; its windows were read as other windows")
     if raise_on_error and flags.value & DEVERR_BAD_FRAME:
         raise MerlinNativeError("merlin_render_frames: an agent outside the grid, on a wall or with a direction outside "
-                                "0..3; its frame was drawn without the agent")
+                                "0..3; its frame was drawn without the agent (merlin_view_codes: its codes are zero)")
     return flags.value
 
 def segment_sum(src, plan, out_rows: int, slot=None, sub: int = 1, name: str = "k_seg_sum", out=None,
