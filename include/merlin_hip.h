@@ -57,7 +57,8 @@
  *                        conv3 / fc1 GEMMs and the heads' backward (actor_critic.py:14-41)
  *
  * What the benched loop (bench.py, BASELINE cfg 2) calls, per rollout step: merlin_tower_codes_conv3_amax,
- * merlin_h3_gemm_nt_heads (cfg 12, heads only), merlin_env_act_step, merlin_env_refill; per update:
+ * merlin_h3_gemm_nt_heads (cfg 12, heads only), merlin_env_act_step; per rollout: merlin_env_refill (the ring of
+ * look-ahead maps topped up once, merlin_env_set_lookahead_depth); per update:
  * merlin_gae, merlin_adv_normalize, merlin_minibatch_patch_maps, and per optimizer step merlin_window_lut_*,
  * merlin_window_gemm_fwd / _bwd, merlin_tower_window_conv3_planes, merlin_h3_gemm_nt_heads (cfg 60),
  * merlin_ppo_loss*, merlin_tower_head_bwd_planes, merlin_h3_gemm_nt_planes (cfg 62),
@@ -224,6 +225,18 @@ int merlin_env_refill(merlin_env *env, void *stream);
  * the pass off (one launch -- one graph node -- fewer per step); an empty slot then raises MERLIN_DEVERR_SLOT_EMPTY
  * (merlin_env_errors) and that step's results are invalid. */
 int merlin_env_set_step_fallback(merlin_env *env, int32_t on);
+/* The look-ahead slot is the head of a ring of `depth` maps per env (default 1: the single slot above, same layout).
+ * Slot j holds the env's j-th next map and the RNG state after generating it; slot j + 1 is generated from that
+ * state, an auto-reset or merlin_env_reset takes the oldest map, so results are the same at every depth.
+ * merlin_env_refill tops every ring up until it is full; a reset that meets an empty ring behaves as one that meets
+ * an empty slot.  At depth > 1 with refill interval 0, merlin_env_reset is not followed by a refill: the caller tops
+ * up.  A ring that is full when a caller starts serves `depth` resets per env with no refill in between -- a rollout
+ * of T steps with the reset at its top uses at most T + 1 (PPO: depth T + 1, one top-up between rollouts, step
+ * fallback off).  Nothing may top up a ring while a step or reset of the same env may run.
+ * [sync] depth in [1, 65535]; reallocates the ring (num_envs * depth * (4 * SP + 40) bytes, SP = 16 up to size 16,
+ * else 32) and drops every look-ahead map; synchronises the device, so it is valid only outside a stream capture,
+ * and launches captured before it must be captured again. */
+int merlin_env_set_lookahead_depth(merlin_env *env, int32_t depth);
 /* The fully observable observation (FullyObsWrapper + ImgObsWrapper, src/scenario_creator/scenario_creator.py:45-50,
  * observation.fully_observable in src/config/scenario.yaml) of every env's current state: out_dev uint8[N][size][size]
  * [3], out[i][x][y] = minigrid Grid.encode's (object, color, state) of cell (x, y), the agent's cell (10, 0, dir).

@@ -506,6 +506,8 @@ int merlin_env_create(const merlin_env_config *cfg, merlin_env **out) {
     alloc((void **)&d.pg_rng_s, n * sizeof(ulonglong2));
     alloc((void **)&d.pg_rng_b, n * sizeof(uint2));
     alloc((void **)&d.pg_valid, n * sizeof(uint8_t));
+    alloc((void **)&d.pg_ring, n * sizeof(uint32_t));
+    d.pg_depth = 1;
     alloc((void **)&d.rflag, n * sizeof(uint8_t));
     alloc((void **)&d.bflag, (n + 63) / 64);  // one flag per step block (merlin_env.hip SBLK >= 64 envs)
     if (d.explore_on) alloc((void **)&d.visited, n * d.sp * sizeof(uint32_t));
@@ -522,7 +524,8 @@ int merlin_env_destroy(merlin_env *e) {
     if (!e) return MERLIN_OK;
     merlin::EnvDev &d = e->dev;
     void *ptrs[] = {d.walls, d.agent, d.rng_s, d.rng_i, d.rng_b, d.ep_ret, d.ep_len, d.err, d.visited,
-                    d.pg_walls, d.pg_agent, d.pg_rng_s, d.pg_rng_b, d.pg_valid, d.rflag, d.bflag, e->diff_buf};
+                    d.pg_walls, d.pg_agent, d.pg_rng_s, d.pg_rng_b, d.pg_valid, d.pg_ring, d.rflag, d.bflag,
+                    e->diff_buf};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     delete e;
@@ -531,6 +534,15 @@ int merlin_env_destroy(merlin_env *e) {
 
 int merlin_env_num_envs(const merlin_env *e) { return e ? e->dev.n : -1; }
 int merlin_env_size(const merlin_env *e) { return e ? e->dev.size : -1; }
+
+// head = count = 0 for every env: the rings' maps are stale (new seeds, new classes, a new depth)
+static hipError_t drop_lookahead(merlin_env *e, hipStream_t s) {
+    const size_t N = (size_t)e->dev.n;
+    hipError_t err = merlin::zero_async(e->dev.pg_valid, N, s);
+    if (err == hipSuccess) err = merlin::zero_async(e->dev.pg_ring, N * sizeof(uint32_t), s);
+    e->seed_slots_full = false;
+    return err;
+}
 
 int merlin_env_seed(merlin_env *e, const uint64_t *seeds, int32_t n, void *stream) {
     if (!e || !seeds) return fail(MERLIN_E_INVALID, "null argument");
@@ -549,7 +561,7 @@ int merlin_env_seed(merlin_env *e, const uint64_t *seeds, int32_t n, void *strea
     if (err == hipSuccess)
         err = hipMemcpyAsync(e->dev.rng_i, inc, N * sizeof(ulonglong2), hipMemcpyHostToDevice, s);
     if (err == hipSuccess) err = merlin::zero_async(e->dev.rng_b, N * sizeof(uint2), s);
-    if (err == hipSuccess) err = merlin::zero_async(e->dev.pg_valid, N, s);  // look-ahead maps are stale
+    if (err == hipSuccess) err = drop_lookahead(e, s);  // look-ahead maps are stale
     e->seed_slots_full = false;
     if (err == hipSuccess) err = hipStreamSynchronize(s);  // host staging buffers are freed below
     delete[] st;
@@ -578,7 +590,7 @@ int merlin_env_set_difficulties(merlin_env *e, const int32_t *diff, int32_t n, v
     } else {
         e->dev.diff = nullptr;
     }
-    if (err == hipSuccess) err = merlin::zero_async(e->dev.pg_valid, N, s);  // look-ahead maps are stale
+    if (err == hipSuccess) err = drop_lookahead(e, s);  // look-ahead maps are stale
     e->seed_slots_full = false;
     if (err == hipSuccess) err = hipStreamSynchronize(s);  // the host staging buffer is freed below
     delete[] host;
@@ -588,11 +600,14 @@ int merlin_env_set_difficulties(merlin_env *e, const int32_t *diff, int32_t n, v
 
 int merlin_env_reset(merlin_env *e, const uint8_t *mask, uint32_t *obs, void *stream) {
     if (!e) return fail(MERLIN_E_INVALID, "null env");
-    HIP_TRY(merlin::launch_env_reset(e->dev, mask, obs, (hipStream_t)stream));  // + look-ahead refill
+    // + look-ahead refill; a deeper ring whose refills are the caller's (interval 0) is topped up by the caller too
+    const bool refill = e->dev.pg_depth == 1 || e->refill_every > 0;
+    HIP_TRY(merlin::launch_env_reset(e->dev, mask, obs, refill, (hipStream_t)stream));
     e->steps_since_refill = 0;
     if (!mask) {
         e->has_state = true;
-        e->seed_slots_full = e->dev.reseed != 0;  // the reset's full refill filled every slot with its seed map
+        // the reset's full refill filled every slot with its seed map
+        e->seed_slots_full = e->dev.reseed != 0 && refill;
     }
     return MERLIN_OK;
 }
@@ -685,7 +700,41 @@ int merlin_env_set_refill_interval(merlin_env *e, int32_t every) {
 
 int merlin_env_refill(merlin_env *e, void *stream) {
     if (!e) return fail(MERLIN_E_INVALID, "null env");
-    HIP_TRY(merlin::launch_env_refill(e->dev, false, (hipStream_t)stream));
+    // a deeper ring is the caller's to top up between runs of steps, when most envs have used a map or several:
+    // one wave per 64 envs, all generating at once, as after a full reset
+    HIP_TRY(merlin::launch_env_refill(e->dev, e->dev.pg_depth > 1, (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_env_set_lookahead_depth(merlin_env *e, int32_t depth) {
+    if (!e) return fail(MERLIN_E_INVALID, "null env");
+    if (depth < 1 || depth > 65535) return fail(MERLIN_E_INVALID, "look-ahead depth must be in [1, 65535]");
+    merlin::EnvDev &d = e->dev;
+    HIP_TRY(hipDeviceSynchronize());  // nothing in flight reads the old ring (fails inside a capture)
+    const size_t slots = (size_t)d.n * (size_t)depth;
+    void *p[4] = {nullptr, nullptr, nullptr, nullptr};
+    const size_t bytes[4] = {slots * d.sp * sizeof(uint32_t), slots * sizeof(uint4), slots * sizeof(ulonglong2),
+                             slots * sizeof(uint2)};
+    hipError_t err = hipSuccess;
+    for (int k = 0; k < 4 && err == hipSuccess; k++) {
+        err = hipMalloc(&p[k], bytes[k]);
+        if (err == hipSuccess) err = hipMemset(p[k], 0, bytes[k]);
+    }
+    if (err != hipSuccess) {  // the env keeps the ring it had
+        for (void *q : p)
+            if (q) (void)hipFree(q);
+        return hip_fail(err, "hipMalloc(look-ahead ring)");
+    }
+    void *old[4] = {d.pg_walls, d.pg_agent, d.pg_rng_s, d.pg_rng_b};
+    for (void *q : old) (void)hipFree(q);
+    d.pg_walls = (uint32_t *)p[0];
+    d.pg_agent = (uint4 *)p[1];
+    d.pg_rng_s = (ulonglong2 *)p[2];
+    d.pg_rng_b = (uint2 *)p[3];
+    d.pg_depth = depth;
+    e->steps_since_refill = 0;
+    HIP_TRY(drop_lookahead(e, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
     return MERLIN_OK;
 }
 

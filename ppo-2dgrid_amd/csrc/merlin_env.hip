@@ -548,11 +548,17 @@ __device__ __forceinline__ void reset_visited(const EnvDev &E, int i, int ax, in
 // refill, or a reseed) generates the same map from the env's RNG: in place in the reset and
 // multi-step kernels, in k_env_fallback after a single-step launch.  In reseed mode (every reset is
 // reset(seed=task_seed)) the slot is never consumed and the env's RNG never advances.
+// The slot is the head of a ring of pg_depth maps (merlin_env_set_lookahead_depth, default 1): slot j holds a map and the
+// RNG state after generating it, the generator of slot j + 1 starts from that state, and a reset takes the oldest
+// map, so env i's k-th map is the same whoever generated it and whenever.  A ring that is full when a caller
+// starts can serve pg_depth resets per env with no refill in between (PPO's rollout: depth T + 1).
 template <int SP, int NB>
 __device__ __forceinline__ bool take_slot(const EnvDev &E, int i, uint32_t (*rows)[NB], int lane, GenOut &g) {
-    if (!E.pg_valid[i]) return false;
+    const uint32_t ring = E.pg_ring[i], head = ring & 0xffffu, count = ring >> 16;
+    if (!count) return false;
     {
-        const uint4 *src = reinterpret_cast<const uint4 *>(E.pg_walls + (size_t)i * SP);
+        const size_t k = (size_t)i * E.pg_depth + head;
+        const uint4 *src = reinterpret_cast<const uint4 *>(E.pg_walls + k * SP);
 #pragma unroll
         for (int q = 0; q < SP / 4; q++) {
             const uint4 v = src[q];
@@ -561,7 +567,7 @@ __device__ __forceinline__ bool take_slot(const EnvDev &E, int i, uint32_t (*row
             rows[4 * q + 2][lane] = v.z;
             rows[4 * q + 3][lane] = v.w;
         }
-        const uint4 a = E.pg_agent[i];
+        const uint4 a = E.pg_agent[k];
         g.ax = a.x & 0xff;
         g.ay = (a.x >> 8) & 0xff;
         g.dir = (a.x >> 16) & 3;
@@ -569,8 +575,9 @@ __device__ __forceinline__ bool take_slot(const EnvDev &E, int i, uint32_t (*row
         g.gy = (a.z >> 8) & 0xff;
         g.err = 0u;
         if (!E.reseed) {
-            E.rng_s[i] = E.pg_rng_s[i];
-            E.rng_b[i] = E.pg_rng_b[i];
+            E.rng_s[i] = E.pg_rng_s[k];
+            E.rng_b[i] = E.pg_rng_b[k];
+            E.pg_ring[i] = (head + 1 == (uint32_t)E.pg_depth ? 0u : head + 1) | ((count - 1) << 16);
             E.pg_valid[i] = 0;
         }
     }
@@ -625,28 +632,52 @@ __global__ __launch_bounds__(BLK) void k_env_reset(EnvDev E, const uint8_t *__re
     reset_one<SP>(E, i, rows, lane, obs);
 }
 
-// Fill the empty look-ahead slots: each one-wave block takes SPAN x 64 envs (SPAN 16: lane l reads the
-// slot flags of envs base + 16*l .. in one 16-B load), packs the empty ones onto consecutive lanes
-// (ballot + prefix count) and generates 64 at a time, one thread per env, from the env's RNG (which
-// stays as it is: the slot holds the state after the generation).  SPAN 4 for the few slots a step
-// uses, SPAN 1 (one wave per 64 envs, all generating at once) after a full reset used every slot.
+// Top up the look-ahead rings: each one-wave block takes SPAN x 64 envs (SPAN 16: lane l reads the
+// ring-full flags of envs base + 16*l .. in one 16-B load), packs the ones whose ring is not full onto
+// consecutive lanes (ballot + prefix count) and serves 64 at a time, one thread per env generating map after
+// map until its ring is full: the first from the state the ring's newest slot holds (the env's own RNG when
+// the ring is empty, which stays as it is), each slot keeping the state after its generation.  In reseed mode
+// only the head is ever read, so one map is a full ring.  SPAN 4 for the few envs a step
+// resets, SPAN 1 (one wave per 64 envs, all generating at once) when every env is short.
 template <int SP>
 __device__ __forceinline__ void refill_one(const EnvDev &E, int i, uint32_t (*rows)[BLK], int lane) {
+    const int D = E.pg_depth, want = E.reseed ? 1 : D;
+    const uint32_t ring = E.pg_ring[i];
+    const int head = (int)(ring & 0xffffu);
+    int count = (int)(ring >> 16);
     Rng r = load_rng(E, i);
-    GenOut g;
-    generate_map_inl<SP, BLK>(rows, lane, E.size, env_difficulty(E, i), r, E.err + 1, g);
-    uint4 *dst = reinterpret_cast<uint4 *>(E.pg_walls + (size_t)i * SP);
-#pragma unroll
-    for (int q = 0; q < SP / 4; q++) {
-        const int y = 4 * q;
-        dst[q] = make_uint4(y + 0 < E.size ? rows[y + 0][lane] : 0u, y + 1 < E.size ? rows[y + 1][lane] : 0u,
-                            y + 2 < E.size ? rows[y + 2][lane] : 0u, y + 3 < E.size ? rows[y + 3][lane] : 0u);
+    if (count) {
+        const int last = head + count - 1;
+        const size_t k = (size_t)i * D + (last >= D ? last - D : last);
+        const ulonglong2 s = E.pg_rng_s[k];
+        const uint2 b = E.pg_rng_b[k];
+        r.slo = s.x;
+        r.shi = s.y;
+        r.has = b.x;
+        r.buf = b.y;
     }
-    E.pg_agent[i] = pack_agent(g.ax, g.ay, g.dir, 0, g.gx, g.gy, g.ax, g.ay, 0);
-    E.pg_rng_s[i] = make_ulonglong2(r.slo, r.shi);
-    E.pg_rng_b[i] = make_uint2(r.has, r.buf);
+    const int difficulty = env_difficulty(E, i);
+    uint32_t err = 0u;
+    for (; count < want; count++) {
+        const int slot = head + count;
+        const size_t k = (size_t)i * D + (slot >= D ? slot - D : slot);
+        GenOut g;
+        generate_map_inl<SP, BLK>(rows, lane, E.size, difficulty, r, E.err + 1, g);
+        uint4 *dst = reinterpret_cast<uint4 *>(E.pg_walls + k * SP);
+#pragma unroll
+        for (int q = 0; q < SP / 4; q++) {
+            const int y = 4 * q;
+            dst[q] = make_uint4(y + 0 < E.size ? rows[y + 0][lane] : 0u, y + 1 < E.size ? rows[y + 1][lane] : 0u,
+                                y + 2 < E.size ? rows[y + 2][lane] : 0u, y + 3 < E.size ? rows[y + 3][lane] : 0u);
+        }
+        E.pg_agent[k] = pack_agent(g.ax, g.ay, g.dir, 0, g.gx, g.gy, g.ax, g.ay, 0);
+        E.pg_rng_s[k] = make_ulonglong2(r.slo, r.shi);
+        E.pg_rng_b[k] = make_uint2(r.has, r.buf);
+        err |= g.err;
+    }
+    E.pg_ring[i] = (uint32_t)head | ((uint32_t)count << 16);
     E.pg_valid[i] = 1;
-    if (g.err) atomicOr(E.err, g.err);
+    if (err) atomicOr(E.err, err);
 }
 
 template <int SP, int SPAN>
@@ -900,14 +931,14 @@ hipError_t launch_env_refill(const EnvDev &E, bool full, hipStream_t s) {
     return E.sp == 16 ? launch_refill_sp<16>(E, full, s) : launch_refill_sp<32>(E, full, s);
 }
 
-hipError_t launch_env_reset(const EnvDev &E, const uint8_t *mask, uint32_t *obs, hipStream_t s) {
+hipError_t launch_env_reset(const EnvDev &E, const uint8_t *mask, uint32_t *obs, bool refill, hipStream_t s) {
     const dim3 grid((E.n + BLK - 1) / BLK), block(BLK);
     if (E.sp == 16)
         hipLaunchKernelGGL(k_env_reset<16>, grid, block, 0, s, E, mask, obs);
     else
         hipLaunchKernelGGL(k_env_reset<32>, grid, block, 0, s, E, mask, obs);
     hipError_t e = hipGetLastError();
-    return e != hipSuccess ? e : launch_env_refill(E, mask == nullptr, s);
+    return (e != hipSuccess || !refill) ? e : launch_env_refill(E, mask == nullptr, s);
 }
 
 template <int SP>

@@ -20,9 +20,11 @@ namespace merlin {
 //   ep_len  int32[n]
 //   visited uint32[n][SP]   exploration-bonus visit bitmask (only if enabled)
 //   err     uint32[2]       device error bits, fallback-map counter
-//   pg_*    the env's look-ahead map (merlin_env.hip k_env_refill): pg_walls uint32[n][SP],
-//           pg_agent uint4[n] (agent format above), pg_rng_s / pg_rng_b (RNG state after it),
-//           pg_valid uint8[n] (1 = the slot holds the env's next map)
+//   pg_*    the env's ring of D = pg_depth look-ahead maps (merlin_env.hip k_env_refill), env-major: pg_walls
+//           uint32[n][D][SP], pg_agent uint4[n][D] (agent format above), pg_rng_s / pg_rng_b [n][D] (RNG state after
+//           generating that map: the next slot's generator starts from it), pg_ring uint32[n] (consume index |
+//           fill count << 16), pg_valid uint8[n] (1 = the ring is full: nothing for the refill to do; at D = 1
+//           "the slot holds the env's next map")
 //   rflag   uint8[n]        1 = reset due, its slot was empty (single-step launch; k_env_fallback)
 //   bflag   uint8[ceil(n/64)] 1 = some env of that step block (SBLK envs, merlin_env.hip) is flagged
 //   diff    uint8[n]        the env's map generator (MERLIN_* id); null = the uniform `difficulty`
@@ -47,6 +49,8 @@ struct EnvDev {
     ulonglong2 *pg_rng_s;
     uint2 *pg_rng_b;
     uint8_t *pg_valid;
+    uint32_t *pg_ring;
+    int pg_depth;
     uint8_t *rflag;
     uint8_t *bflag;
     const uint8_t *diff;  // per-env generator class uint8[n] (merlin_env_set_difficulties); null: `difficulty` for all
@@ -305,7 +309,7 @@ void set_h3p_walk_blocks(int n);
 hipError_t launch_h3p_gemm_tn_gather(const void *A, const uint32_t *amaxA, const void *B, const uint32_t *amaxB,
                                      int64_t Kd, int M, int N, int T, int64_t a_stride, int64_t b_stride, int splits,
                                      float *slab, const int32_t *b_rows, int cfg, int *S_out, hipStream_t s);
-hipError_t launch_env_reset(const EnvDev &E, const uint8_t *mask, uint32_t *obs, hipStream_t s);
+hipError_t launch_env_reset(const EnvDev &E, const uint8_t *mask, uint32_t *obs, bool refill, hipStream_t s);
 hipError_t launch_env_step(const EnvDev &E, const StepOut &O, bool refill, hipStream_t s);
 hipError_t launch_env_full_obs(const EnvDev &E, uint8_t *out, hipStream_t s);
 hipError_t launch_env_refill(const EnvDev &E, bool full, hipStream_t s);

@@ -90,6 +90,7 @@ def lib():
     L.merlin_env_set_refill_interval.argtypes = [vp, i32]
     L.merlin_env_set_step_fallback.argtypes = [vp, i32]
     L.merlin_env_refill.argtypes = [vp, vp]
+    L.merlin_env_set_lookahead_depth.argtypes = [vp, i32]
     L.merlin_env_get_state.argtypes = [vp, vp, vp, vp, vp]
     L.merlin_env_full_obs.argtypes = [vp, vp, vp]
     L.merlin_env_errors.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp]
@@ -223,7 +224,7 @@ def check_env_config_layout(L) -> None:
 EXPORTED_SYMBOLS = (
     "merlin_version", "merlin_last_error", "merlin_tile_atlas", "merlin_env_config_layout", "merlin_env_create",
     "merlin_env_destroy", "merlin_env_seed", "merlin_env_reset", "merlin_env_step", "merlin_env_act_step", "merlin_group_act",
-    "merlin_env_set_refill_interval", "merlin_env_refill",
+    "merlin_env_set_refill_interval", "merlin_env_refill", "merlin_env_set_lookahead_depth",
     "merlin_env_get_state", "merlin_env_full_obs", "merlin_env_errors", "merlin_env_set_step_fallback", "merlin_env_num_envs", "merlin_env_size",
     "merlin_obs_expand_f32", "merlin_obs_expand_u8", "merlin_gae", "merlin_adv_normalize",
     "merlin_conv1_lut_fwd", "merlin_conv1_lut_bwd", "merlin_tower_conv2_im2col_fwd",

@@ -103,6 +103,9 @@ class MerlinVecEnv:
             h = C.c_void_p()
             nat.check(self._lib.merlin_env_create(C.byref(cfg), C.byref(h)), "merlin_env_create")
         self._h = h
+        self.lookahead_depth = 1  # set_lookahead_depth
+        self.step_fallback = True  # set_step_fallback
+        self._topup = None  # the stream a refill(stream=...) not yet joined runs on
         self.class_ids = torch.full((self.num_envs,), nat.DIFFICULTY_IDS[uniform], dtype=torch.uint8,
                                     device=self.device)
         # True once classes are assigned: the kernels then read the context's class buffer instead of the uniform id
@@ -145,6 +148,7 @@ class MerlinVecEnv:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def seed(self, seed: int) -> None:
+        self.join_refill()
         seeds = (np.arange(self.num_envs, dtype=np.uint64) + np.uint64(self.env_offset)
                  + np.uint64(seed))
         with torch.cuda.device(self.device):
@@ -163,6 +167,7 @@ class MerlinVecEnv:
         """Seed env i with seeds[i] (e.g. FOMAML task seeds)."""
         seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64))
         assert seeds.shape == (self.num_envs,)
+        self.join_refill()
         with torch.cuda.device(self.device):
             nat.check(self._lib.merlin_env_seed(self._h, seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
                                                 self.num_envs, self._stream), "merlin_env_seed")
@@ -183,6 +188,7 @@ class MerlinVecEnv:
         device buffer of the context, so step / reset launches captured into a graph after the first call read a later
         call's classes without a re-capture.  None restores the constructor's uniform difficulty (and unbinds the
         buffer).  Syncs the current stream."""
+        self.join_refill()
         if names is None:
             with torch.cuda.device(self.device):
                 nat.check(self._lib.merlin_env_set_difficulties(self._h, None, 0, self._stream),
@@ -197,6 +203,7 @@ class MerlinVecEnv:
     def set_class_ids(self, ids) -> None:
         """set_difficulties by MERLIN_* id (int32[num_envs]); the library validates the ids."""
         ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32))
+        self.join_refill()
         with torch.cuda.device(self.device):
             nat.check(self._lib.merlin_env_set_difficulties(self._h, ids.ctypes.data_as(C.POINTER(C.c_int32)),
                                                             int(ids.size), self._stream),
@@ -207,12 +214,19 @@ class MerlinVecEnv:
         self.class_ids.copy_(torch.from_numpy(ids.astype(np.uint8)))
         self.per_env_classes = True
 
+    def ensure_seeded(self) -> None:
+        """Seed the envs now if nothing has yet (the constructor's or set_base_seed's seed, else entropy), as the
+        first reset() given no seed would: a caller that refills the look-ahead maps before that reset needs the
+        seeds in place, since seeding drops every look-ahead map."""
+        if not self._seeded_once:
+            self.seed(self._seed_pending if self._seed_pending is not None else _entropy_seed())
+
     def reset(self, seed: int | None = None, mask: torch.Tensor | None = None, out: torch.Tensor | None = None):
         """Reset all envs (or those with mask != 0).  Returns the obs codes int32[N, 8]."""
-        if seed is None and not self._seeded_once:
-            seed = self._seed_pending if self._seed_pending is not None else _entropy_seed()
+        self.join_refill()
         if seed is not None:
             self.seed(seed)
+        self.ensure_seeded()
         out = self.obs if out is None else out
         if mask is not None:
             mask = mask.to(torch.uint8).contiguous()
@@ -235,6 +249,7 @@ class MerlinVecEnv:
         t*action_stride + i (state stays on chip across the steps)."""
         assert actions.dtype == torch.int64 and actions.is_contiguous()
         stride = self.num_envs if action_stride is None else int(action_stride)
+        self.join_refill()
         with torch.cuda.device(self.device), nat.KernelTimer.span("k_env_step", self.num_envs * n_steps * ENV_STEP_BYTES):
             nat.check(self._lib.merlin_env_step(
                 self._h, nat.ptr(actions), int(n_steps), stride, nat.ptr(obs_out), nat.ptr(reward),
@@ -255,6 +270,7 @@ class MerlinVecEnv:
         assert b_critic.numel() == 1 and 1 <= A <= 4
         if not deterministic and epoch is None:
             raise ValueError("act_step_into: a sampled action needs an epoch counter tensor (int64[1] on the device)")
+        self.join_refill()
         with torch.cuda.device(self.device), nat.KernelTimer.span("k_env_step", self.num_envs * ENV_STEP_BYTES):
             nat.check(self._lib.merlin_env_act_step(
                 self._h, nat.ptr(part), P, nat.ptr(b_actor), nat.ptr(b_critic), A, int(bool(deterministic)),
@@ -272,13 +288,51 @@ class MerlinVecEnv:
         so the per-step fallback pass is not launched; a reset that meets an empty slot then raises
         DEVERR_SLOT_EMPTY in errors() (merlin_env_set_step_fallback)."""
         nat.check(self._lib.merlin_env_set_step_fallback(self._h, 1 if on else 0), "merlin_env_set_step_fallback")
+        self.step_fallback = bool(on)
 
-    def refill(self) -> None:
-        """Generate the next map of every env whose look-ahead slot was used, on the current stream
-        (merlin_env_refill).  Touches only the slots and reads the envs' RNG: it may run on a side
-        stream beside work that does not step this env, joined before the next step."""
+    def set_lookahead_depth(self, depth: int) -> None:
+        """A ring of `depth` look-ahead maps per env (merlin_env_set_lookahead_depth; default 1, the single slot):
+        refill() tops every ring up until it is full, a reset takes the oldest map, and a ring that is full when a
+        caller starts serves `depth` resets per env with no refill in between.  At depth > 1 with refill interval 0
+        reset() is not followed by a refill.  Results are the same at every depth.  Reallocates the ring
+        (num_envs x depth x 104 B up to size 16, 168 B above), drops every look-ahead map and synchronises the
+        device: not inside a graph capture, and a graph captured before it must be captured again."""
+        self.join_refill()
         with torch.cuda.device(self.device):
+            nat.check(self._lib.merlin_env_set_lookahead_depth(self._h, int(depth)), "merlin_env_set_lookahead_depth")
+        self.lookahead_depth = int(depth)
+
+    def lookahead_bytes(self, depth: int) -> int:
+        """Device bytes of a ring of `depth` look-ahead maps per env (rows, agent + goal, RNG state)."""
+        return self.num_envs * int(depth) * (4 * (16 if self.size <= 16 else 32) + 40)
+
+    def refill(self, stream=None) -> None:
+        """Generate maps until every env's look-ahead ring is full again (at depth 1: the next map of every env
+        whose slot was used), on the current stream (merlin_env_refill).  Touches only the rings and reads the
+        envs' RNG: at depth 1 it may run on a side stream beside work that does not step this env, joined before
+        the next step.  `stream`: run it on that stream behind the work queued on the current one; whatever next
+        seeds, resets, steps or refills this env through this object waits for it first (join_refill; a captured
+        graph that steps the env is the caller's to order: join_refill() before its replay)."""
+        self.join_refill()
+        if stream is None:
+            with torch.cuda.device(self.device):
+                nat.check(self._lib.merlin_env_refill(self._h, self._stream), "merlin_env_refill")
+            return
+        stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.device(self.device), torch.cuda.stream(stream):
             nat.check(self._lib.merlin_env_refill(self._h, self._stream), "merlin_env_refill")
+        self._topup = stream
+
+    @property
+    def refill_pending(self) -> bool:
+        """A refill(stream=...) has been launched and nothing has waited for it yet."""
+        return self._topup is not None
+
+    def join_refill(self) -> None:
+        """The current stream waits for a refill(stream=...) still pending; nothing to do otherwise."""
+        if self._topup is not None:
+            torch.cuda.current_stream(self.device).wait_stream(self._topup)
+            self._topup = None
 
     def step(self, actions: torch.Tensor, autoreset: bool = True):
         """gym-vector style step: returns (obs codes, reward, terminated, truncated, info).

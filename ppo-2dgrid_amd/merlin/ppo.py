@@ -78,6 +78,13 @@ FUSE_ACT_STEP = True
 # the env step's fallback pass in the rollout even when the look-ahead slots are refilled after every step (False:
 # left out there, round 6 -- no reset can meet an empty slot; MerlinVecEnv.set_step_fallback)
 ROLLOUT_STEP_FALLBACK = False
+# the rollout on a ring of T + 1 look-ahead maps per env (MerlinVecEnv.set_lookahead_depth), topped up once between
+# rollouts, when the ring fits this many bytes (False or over budget: one slot per env, refilled on a side stream
+# after every step).  The reset at a rollout's top and at most one auto-reset per step use at most T + 1 maps per
+# env, so a ring that is full when the rollout starts cannot run dry inside it: the per-step fork / join and the
+# fallback node are gone and the captured graph is a linear chain
+ROLLOUT_MAP_RING = True
+ROLLOUT_RING_BUDGET = 1 << 30
 
 
 class PPO:
@@ -167,8 +174,10 @@ class PPO:
             # (MerlinVecEnv.refill; the env's own every-16-steps refill is switched off)
             self._refill_stream = (torch.cuda.Stream(self.device) if self.device.type == "cuda" and self.use_cnn
                                    else None)
+            self._ring = False
             if self._refill_stream is not None:
                 self.vec.set_refill_interval(0)
+                self.set_map_ring(ROLLOUT_MAP_RING)
         else:
             sample_obs, _ = env.reset()
             self.num_envs, self.k_steps, self.batch_size = 1, batch_size, batch_size
@@ -229,6 +238,21 @@ class PPO:
         self._wstep = None
         self._flat_params = flatten_parameters(self.ac)
 
+    def set_map_ring(self, on: bool) -> bool:
+        """The rollout's look-ahead maps: a ring of T + 1 per env topped up between rollouts (on, when it fits
+        ROLLOUT_RING_BUDGET), or one slot per env refilled on a side stream after every step.  Returns what is in
+        effect.  Changes no result; drops the captured rollout graph (it holds the env's ring addresses)."""
+        if getattr(self, "_refill_stream", None) is None:
+            return False
+        depth = self.k_steps + 1
+        ring = bool(on) and self.vec.lookahead_bytes(depth) <= ROLLOUT_RING_BUDGET
+        if ring != self._ring or self.vec.lookahead_depth != (depth if ring else 1):
+            torch.cuda.synchronize(self.device)
+            self._graph = None
+            self.vec.set_lookahead_depth(depth if ring else 1)
+            self._ring = ring
+        return ring
+
     def collect_rollouts(self):
         if self.vec is None:
             return self._collect_rollouts_single()
@@ -236,6 +260,15 @@ class PPO:
             return self._collect_rollouts_flat()
         if self._graph is not None and not self._params_on_flat():
             self._rehome_parameters()  # the graph would read the old parameter storage: re-capture
+        if self._ring:
+            # every ring full before the rollout executes: the top-up launched behind the last rollout has run
+            # beside the update (joined here); before the first rollout, or after anything else used the env since,
+            # top up in-stream (seeding drops the maps, so the seeds go first)
+            if self.vec.refill_pending:
+                self.vec.join_refill()
+            else:
+                self.vec.ensure_seeded()
+                self.vec.refill()
         if self._graph is not None:
             self._graph.replay()
         else:
@@ -244,6 +277,11 @@ class PPO:
                 self._capture_rollout()
         self._record_episodes()
         self.vec.errors()
+        if self._ring:
+            # placed by executions of the rollout (a capture executes nothing), outside the graph: the maps this
+            # rollout used, generated on the side stream beside GAE and the update.  Launched after errors() so that
+            # the error word is not cleared under a generator that reports into it
+            self.vec.refill(stream=self._refill_stream)
         if self.rollout_all_windows:
             nat.tower_errors(self.device)  # the compact acting table saw only observations
         lv = self.buf.last_value
@@ -252,7 +290,10 @@ class PPO:
     def _rollout_body(self):
         """ppo.py:64-105 for N envs: reset (ppo.py:65: every rollout starts from a fresh
         reset), T x (act -> env step writing into the [T][N] storage), bootstrap value.
-        After every `refill_every`-th step the used look-ahead map slots are refilled on a side stream,
+        On the map ring (set_map_ring) every env holds the T + 1 maps the rollout can use at most, so per step it is
+        act -> (draw +) step on one stream, no refill, no fallback pass: a linear chain (collect_rollouts tops the
+        rings up between rollouts).  Otherwise
+        after every `refill_every`-th step the used look-ahead map slots are refilled on a side stream,
         beside the next act (which reads only the obs codes), and joined before the next step.  (A
         refill's ~60 us of map generation is as long as the act beside it, so refilling after every step
         put it on the step's critical path; an env whose slot is still empty when it resets again takes
@@ -261,9 +302,14 @@ class PPO:
         T = buf.T
         main, side = torch.cuda.current_stream(self.device), self._refill_stream
         every = max(1, int(self.refill_every))
-        # refilled after every step and joined before the next: no reset can meet an empty slot, so the step's
-        # fallback pass (a graph node per step, ~4 us + its dispatch gap) is left out; errors() would report one
-        env.set_step_fallback(ROLLOUT_STEP_FALLBACK or side is None or every != 1)
+        fallback_was = env.step_fallback
+        if self._ring:
+            side = None
+            env.set_step_fallback(ROLLOUT_STEP_FALLBACK)
+        else:
+            # refilled after every step and joined before the next: no reset can meet an empty slot, so the step's
+            # fallback pass (a graph node per step, ~4 us + its dispatch gap) is left out; errors() would report one
+            env.set_step_fallback(ROLLOUT_STEP_FALLBACK or side is None or every != 1)
         env.reset(out=buf.codes[0])
         with torch.no_grad():
             self._act_epoch.add_(1)
@@ -300,6 +346,9 @@ class PPO:
             if pending:
                 main.wait_stream(side)
             buf.last_value.copy_(last_value)
+        # the flag is read on the host at launch (a captured graph keeps what it captured): whoever steps the env
+        # after the rollout gets the fallback pass back
+        env.set_step_fallback(fallback_was)
 
     def _capture_rollout(self):
         """Record _rollout_body as one HIP graph (torch.cuda.graph; the env and lookup kernels

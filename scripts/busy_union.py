@@ -80,3 +80,19 @@ for a, b in list(zip(bounds, ends))[-3:]:
         agg[k[:60]] = (n + 1, tot + e - s)
     for k, (n, tot) in sorted(agg.items(), key=lambda x: -x[1][1])[:8]:
         print(f"    {k:60s} {n:5d} x {tot / n / 1e3:7.1f} us")
+    # the launches a step chains (act's conv3 lookup, the fc1 + heads GEMM, draw + env step): their sum is the period
+    # a linear graph could reach with no dispatch gap
+    chain = [tot / n / 1e3 for k, (n, tot) in agg.items()
+             if any(c in k for c in ("k_codes_conv3", "k_h3_ntp", "k_env_step"))]
+    print(f"    step period {per:.1f} us against the chained kernels' sum {sum(chain):.1f} us "
+          f"({' + '.join(f'{c:.1f}' for c in sorted(chain, reverse=True))})")
+
+# the look-ahead map refills outside the rollout spans (the ring's top-up: one per iteration, beside the update)
+for a, b in runs[-6:]:
+    t0 = rows[a][0]
+    ref = [(s, e) for s, e, k in rows[a:b] if "k_env_refill" in k]
+    if ref:
+        print(f"update: {len(ref)} k_env_refill outside the rollout: " + ", ".join(
+            f"{(e - s) / 1e3:.0f} us at +{(s - t0) / 1e6:.2f} ms" for s, e in ref[:4]))
+    else:
+        print("update: no k_env_refill outside the rollout")
