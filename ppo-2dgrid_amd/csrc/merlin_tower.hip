@@ -302,7 +302,10 @@ __global__ __launch_bounds__(BLK) void k_col2im3_bwd_chunked(const float4 *__res
                                                              float4 *__restrict__ dZ2c,
                                                              uint32_t *__restrict__ absmax) {
     __shared__ float4 tile[CF * P3 * K3 / 4];
-    float amax = 0.0f;
+    // max |dZ2| as float bits with the sign cleared: they order like the magnitudes and put every NaN above +inf
+    // (fmaxf would drop a NaN operand instead of keeping it)
+    uint32_t amax = 0u;
+    auto mag = [](float v) { return __float_as_uint(v) & 0x7fffffffu; };
     const int64_t groups = (n + CF - 1) / CF;
     for (int64_t tg = blockIdx.x; tg < (int64_t)T * groups; tg += gridDim.x) {
         const int t = (int)(tg / groups);
@@ -332,16 +335,15 @@ __global__ __launch_bounds__(BLK) void k_col2im3_bwd_chunked(const float4 *__res
             const float4 d = make_float4(z.x + b.x > 0.0f ? g.x : 0.0f, z.y + b.y > 0.0f ? g.y : 0.0f,
                                          z.z + b.z > 0.0f ? g.z : 0.0f, z.w + b.w > 0.0f ? g.w : 0.0f);
             dZ2c[(((size_t)t * 16 + ci4) * n + s0 + f) * P2 + p2] = d;
-            amax = fmaxf(amax, fmaxf(fmaxf(fabsf(d.x), fabsf(d.y)), fmaxf(fabsf(d.z), fabsf(d.w))));
+            amax = max(amax, max(max(mag(d.x), mag(d.y)), max(mag(d.z), mag(d.w))));
         }
     }
     // NaN/inf propagate as a non-finite max (the histogram then returns NaN)
-    for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
-    if (amax != amax) amax = __int_as_float(0x7f800000);
+    for (int off = 32; off > 0; off >>= 1) amax = max(amax, __shfl_xor(amax, off));
+    amax = min(amax, 0x7f800000u);
     // skip the same-address atomic when the word already holds at least this wave's max (it only grows)
-    if ((threadIdx.x & 63) == 0 &&
-        __float_as_uint(amax) > __hip_atomic_load(absmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-        atomicMax(absmax, __float_as_uint(amax));
+    if ((threadIdx.x & 63) == 0 && amax > __hip_atomic_load(absmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        atomicMax(absmax, amax);
 }
 
 int grid_cap(int64_t rows) { return (int)std::max<int64_t>(1, std::min<int64_t>(rows, 256 * 16)); }

@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import lut_hist_ref
 from test_conv2_tables import lut2_rows
 
 pytestmark = pytest.mark.gpu
@@ -74,14 +75,13 @@ def test_lut_histogram_matches_index_add(device, n, use_index):
     dT = nat.conv2_lut_bwd(codes.index_select(0, idx) if use_index else codes, dZ2c)
     sel = idx.cpu().numpy() if use_index else np.arange(n)
     rows = torch.from_numpy(lut2_rows(c49[sel])).to(device).reshape(n * 25, 16)
-    ref = torch.zeros(2, 2720, 64, dtype=torch.float64, device=device)
-    mag = torch.zeros_like(ref)  # sum of |terms| per bin: the scale of fp32 summation error
-    for k in range(16):
-        for t in range(2):
-            ref[t].index_add_(0, rows[:, k], g[t].double())
-            mag[t].index_add_(0, rows[:, k], g[t].double().abs())
+    # each of a bin's count non-zero terms is rounded to 2^-K once and the sum to float32 once (tests/lut_hist_ref.py;
+    # tests/test_gpu_conv2lut_seams.py holds the same kernels bit for bit)
+    ref, count = lut_hist_ref.hist64(rows, g)
+    K = lut_hist_ref.fixed_exp(g.abs().max().item(), n)
     err = (dT.double() - ref).abs()
-    assert (err <= 1e-5 * mag + 1e-6).all(), (err / (mag + 1e-6)).max().item()
+    tol = lut_hist_ref.tolerance(ref, count, K)
+    assert (err <= tol).all(), (err - tol).max().item()
 
 
 @pytest.mark.parametrize("impl", ["lut2", "gemm"])
