@@ -824,6 +824,23 @@ int merlin_stage_tables_fwd(const float *W1_dev, const float *b1_dev, const floa
 int merlin_stage_tables_bwd(const float *W2_dev, const float *HT_dev, const float *dT2_dev, const float *atlas_dev,
                             const int16_t *koff_dev, const int16_t *kv_dev, int32_t towers, float *dH_dev,
                             float *dW1_dev, float *db1_dev, float *dW2_dev, void *stream);
+/* The weight-only chain of the optimizer step (merlin/fast_step.py NATIVE_CHAIN), same bits as the entry points above
+ * with their torch neighbours:
+ * merlin_stage_fwd_planes: merlin_stage_tables_fwd and, when x0_dev is given, merlin_h3_split of x0_dev / x1_dev
+ *   (float [towers][n], n % 8 == 0) at the scale amax_dev[tower] into planes0_dev / planes1_dev, in one launch.
+ * merlin_stage_bwd_scatter: merlin_stage_tables_bwd with dW1 / db1 / dW2 at offsets off_w1 / off_b1 / off_w2 of the
+ *   derived-gradient buffer DG_dev, then flat_dev[map_dev[i]] = DG_dev[i] for i < n (map: distinct int32 indices
+ *   into flat_dev) in the fold's launch: three launches.
+ * merlin_gather_f32: dst_dev[i] = src_dev[map_dev[i]], i < n. */
+int merlin_stage_fwd_planes(const float *W1_dev, const float *b1_dev, const float *W2_dev, const float *atlas_dev,
+                            const int16_t *idx_dev, int32_t towers, float *HT_dev, float *T2_dev, const float *x0_dev,
+                            const float *x1_dev, int64_t n, const uint32_t *amax_dev, void *planes0_dev,
+                            void *planes1_dev, void *stream);
+int merlin_stage_bwd_scatter(const float *W2_dev, const float *HT_dev, const float *dT2_dev, const float *atlas_dev,
+                             const int16_t *koff_dev, const int16_t *kv_dev, int32_t towers, float *dH_dev,
+                             float *DG_dev, int64_t off_w1, int64_t off_b1, int64_t off_w2, const int32_t *map_dev,
+                             int64_t n, float *flat_dev, void *stream);
+int merlin_gather_f32(const float *src_dev, const int32_t *map_dev, int64_t n, float *dst_dev, void *stream);
 
 /* Optimizer step of PPO.update (src/ppo.py:153-156: clip_grad_norm_(params, max_norm) then
  * Adam.step(), replacing torch.nn.utils.clip_grad_norm_ + torch.optim.Adam(fused=True).step()) over
@@ -837,6 +854,19 @@ int64_t merlin_clip_adam_workspace(int32_t n_tensors, const int64_t *numel);
 int merlin_clip_adam(int32_t n_tensors, float *const *params, float *const *grads, float *const *exp_avg,
                      float *const *exp_avg_sq, float *const *steps, const int64_t *numel, double lr, double beta1,
                      double beta2, double eps, float max_norm, float *norm_out, double *workspace, void *stream);
+/* merlin_clip_adam with its neighbours in the fast step's weight-only chain folded into the same two launches (the
+ * parameters get the same bits).  Every params[i] lies in the flat buffer flat_dev[n_flat].  The first launch also
+ * zeroes zero0_dev[n_zero0] and zero1_dev[n_zero1] (32-bit words, plain stores; NULL / 0: none).  The second also
+ * writes each stepped value to its slots of the derived-weight buffer D_dev: slots_dev is int32 [n_flat][2], the (at
+ * most two) indices into D_dev of each element of flat_dev, -1 = none.  For a tensor with amax_slot[i] >= 0 (host
+ * array of n_tensors, NULL: none) it folds max |p| as float bits into amax_dev[amax_slot[i]] by atomicMax (the caller
+ * has that word in a zero list).  total_dev (double[1], NULL: none) becomes total_dev[0] + (double)norm. */
+int merlin_clip_adam_chain(int32_t n_tensors, float *const *params, float *const *grads, float *const *exp_avg,
+                           float *const *exp_avg_sq, float *const *steps, const int64_t *numel, double lr, double beta1,
+                           double beta2, double eps, float max_norm, float *norm_out, double *workspace,
+                           uint32_t *zero0_dev, int32_t n_zero0, uint32_t *zero1_dev, int32_t n_zero1,
+                           const float *flat_dev, int64_t n_flat, const int32_t *slots_dev, float *D_dev,
+                           uint32_t *amax_dev, const int32_t *amax_slot, double *total_dev, void *stream);
 
 /* Few-shot evaluation's inner step (src/distribution_over_tasks.py:200-203, src/fomaml.py:180-182:
  * clip_grad_norm_(fast.parameters(), max_norm) then SGD(lr).step()) for G independent parameter sets at once,

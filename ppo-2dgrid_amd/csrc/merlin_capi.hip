@@ -1291,6 +1291,43 @@ int merlin_stage_tables_bwd(const float *W2, const float *HT, const float *dT2, 
     return MERLIN_OK;
 }
 
+int merlin_stage_fwd_planes(const float *W1, const float *b1, const float *W2, const float *atlas, const int16_t *idx,
+                            int32_t towers, float *HT, float *T2, const float *x0, const float *x1, int64_t n,
+                            const uint32_t *amax, void *planes0, void *planes1, void *stream) {
+    if (!W1 || !b1 || !W2 || !atlas || !idx || !HT || !T2) return fail(MERLIN_E_INVALID, "null argument");
+    if (towers < 1 || towers > 2) return fail(MERLIN_E_INVALID, "towers must be 1 or 2");
+    if (x0 && (!x1 || !amax || !planes0 || !planes1)) return fail(MERLIN_E_INVALID, "null plane argument");
+    if (x0 && (n <= 0 || n % 8)) return fail(MERLIN_E_INVALID, "n must be a positive multiple of 8");
+    HIP_TRY(merlin::launch_stage_fwd_planes(W1, b1, W2, atlas, idx, towers, HT, T2, x0, x1, n, amax, planes0, planes1,
+                                            (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_stage_bwd_scatter(const float *W2, const float *HT, const float *dT2, const float *atlas,
+                             const int16_t *koff, const int16_t *kv, int32_t towers, float *dH, float *DG,
+                             int64_t off_w1, int64_t off_b1, int64_t off_w2, const int32_t *map, int64_t n, float *flat,
+                             void *stream) {
+    if (!W2 || !HT || !dT2 || !atlas || !koff || !kv || !dH || !DG || !map || !flat)
+        return fail(MERLIN_E_INVALID, "null argument");
+    if (towers < 1 || towers > 2) return fail(MERLIN_E_INVALID, "towers must be 1 or 2");
+    const int64_t ends[3] = {off_w1 + (int64_t)towers * 32 * 192, off_b1 + (int64_t)towers * 32,
+                             off_w2 + (int64_t)towers * 64 * 32 * 16};
+    if (off_w1 < 0 || off_b1 < 0 || off_w2 < 0 || ends[0] > n || ends[1] > n || ends[2] > n)
+        return fail(MERLIN_E_INVALID, "a gradient segment lies outside DG[:n]");
+    DeviceWs *ws = nullptr;
+    int rc = device_ws(&ws);
+    if (rc != MERLIN_OK) return rc;
+    HIP_TRY(merlin::launch_stage_bwd_scatter(W2, HT, dT2, atlas, koff, kv, towers, dH, DG, off_w1, off_b1, off_w2, map,
+                                             n, flat, ws->stage_part, (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_gather_f32(const float *src, const int32_t *map, int64_t n, float *dst, void *stream) {
+    if (n < 0 || (n > 0 && (!src || !map || !dst))) return fail(MERLIN_E_INVALID, "bad argument");
+    HIP_TRY(merlin::launch_stage_gather(src, map, n, dst, (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
 int merlin_window_gemm_fwd(const float *a2w, const float *W3r, int32_t towers, int64_t nw, float *Q, void *stream) {
     if (!a2w || !W3r || !Q) return fail(MERLIN_E_INVALID, "null argument");
     if (towers < 1 || towers > 2) return fail(MERLIN_E_INVALID, "towers must be 1 or 2");
@@ -1553,6 +1590,38 @@ int merlin_clip_adam(int32_t n_tensors, float *const *params, float *const *grad
     if (blocks > INT32_MAX / 2) return fail(MERLIN_E_INVALID, "too many elements");
     HIP_TRY(merlin::launch_clip_adam(n_tensors, params, grads, exp_avg, exp_avg_sq, steps, numel, lr, beta1, beta2, eps,
                                      max_norm, norm_out, workspace, (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_clip_adam_chain(int32_t n_tensors, float *const *params, float *const *grads, float *const *exp_avg,
+                           float *const *exp_avg_sq, float *const *steps, const int64_t *numel, double lr, double beta1,
+                           double beta2, double eps, float max_norm, float *norm_out, double *workspace,
+                           uint32_t *zero0, int32_t n_zero0, uint32_t *zero1, int32_t n_zero1, const float *flat,
+                           int64_t n_flat, const int32_t *slots, float *D, uint32_t *amax, const int32_t *amax_slot,
+                           double *total, void *stream) {
+    if (n_tensors < 1 || n_tensors > merlin::OPT_MAX_TENSORS)
+        return fail(MERLIN_E_INVALID, "n_tensors must be in [1, 32]");
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !steps || !numel || !workspace || !flat || !slots || !D)
+        return fail(MERLIN_E_INVALID, "null argument");
+    if (n_zero0 < 0 || n_zero1 < 0 || (n_zero0 > 0 && !zero0) || (n_zero1 > 0 && !zero1))
+        return fail(MERLIN_E_INVALID, "bad zero list");
+    if (amax_slot && !amax) return fail(MERLIN_E_INVALID, "amax_slot without amax_dev");
+    merlin::OptChain ch{};
+    for (int i = 0; i < n_tensors; i++) {
+        if (numel[i] <= 0) return fail(MERLIN_E_INVALID, "every tensor needs numel > 0");
+        if (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i] || !steps[i])
+            return fail(MERLIN_E_INVALID, "null tensor pointer");
+        if (params[i] < flat || params[i] + numel[i] > flat + n_flat)
+            return fail(MERLIN_E_INVALID, "a parameter lies outside the flat buffer");
+        ch.amax_slot[i] = amax_slot ? amax_slot[i] : -1;
+        if (ch.amax_slot[i] < -1 || ch.amax_slot[i] > 1) return fail(MERLIN_E_INVALID, "amax_slot must be -1, 0 or 1");
+    }
+    const int64_t blocks = merlin::opt_blocks(n_tensors, numel);
+    if (blocks > INT32_MAX / 2) return fail(MERLIN_E_INVALID, "too many elements");
+    ch.zero[0] = zero0, ch.zero[1] = zero1, ch.n_zero[0] = n_zero0, ch.n_zero[1] = n_zero1;
+    ch.flat = flat, ch.slots = reinterpret_cast<const int2 *>(slots), ch.D = D, ch.amax = amax, ch.total = total;
+    HIP_TRY(merlin::launch_clip_adam(n_tensors, params, grads, exp_avg, exp_avg_sq, steps, numel, lr, beta1, beta2, eps,
+                                     max_norm, norm_out, workspace, (hipStream_t)stream, &ch));
     return MERLIN_OK;
 }
 

@@ -404,6 +404,17 @@ hipError_t launch_stage_fwd(const float *W1, const float *b1, const float *W2, c
 hipError_t launch_stage_bwd(const float *W2, const float *HT, const float *dT2, const float *atlas,
                             const int16_t *koff, const int16_t *kv, int T, float *dH, float *dW1, float *db1,
                             float *dW2, double *ws, hipStream_t s);
+// the fast step's weight-only chain: the forward with fc1's weight planes (x0, x1: [T][n] fp32 each, nullable) in
+// one launch; the backward writing dW1 / db1 / dW2 at offsets w1 / b1 / w2 of DG and scattering DG[:n] to
+// flat[map[:n]] in its fold's launch; dst = src[map]
+hipError_t launch_stage_fwd_planes(const float *W1, const float *b1, const float *W2, const float *atlas,
+                                   const int16_t *idx, int T, float *HT, float *T2, const float *x0, const float *x1,
+                                   int64_t n, const uint32_t *amax, void *planes0, void *planes1, hipStream_t s);
+hipError_t launch_stage_bwd_scatter(const float *W2, const float *HT, const float *dT2, const float *atlas,
+                                    const int16_t *koff, const int16_t *kv, int T, float *dH, float *DG, int64_t w1,
+                                    int64_t b1, int64_t w2, const int32_t *map, int64_t n, float *flat, double *ws,
+                                    hipStream_t s);
+hipError_t launch_stage_gather(const float *src, const int32_t *map, int64_t n, float *dst, hipStream_t s);
 // the window GEMM's backward (csrc/merlin_winbwd.hip): work = winbwd_work_floats(T, nw) floats of scratch
 int64_t winbwd_work_floats(int T, int64_t nw);
 hipError_t launch_winbwd(const float *a2w, const float *dQ, const float *W3r, int T, int64_t nw, float *da2w,
@@ -559,9 +570,22 @@ hipError_t launch_h3_gemm_tn(const void *A, const uint32_t *amaxA, const void *B
 // clip_grad_norm_ + Adam step over a parameter list (merlin_optim.hip)
 constexpr int OPT_MAX_TENSORS = 32;
 int64_t opt_blocks(int n, const int64_t *numel);
+// what the two launches take over from their neighbours in the fast step's weight-only chain (merlin_optim.hip);
+// every parameter lies in the flat buffer `flat`
+struct OptChain {
+    uint32_t *zero[2];  // word lists zeroed by k_opt_sumsq's block 0
+    int n_zero[2];
+    const float *flat;                // the flat parameter buffer
+    const int2 *slots;                // per element of it: its (at most two) slots in D, -1 = none
+    float *D;                         // the derived-weight buffer
+    uint32_t *amax;                   // scale words (float bits of max |p|), zeroed through `zero`
+    int amax_slot[OPT_MAX_TENSORS];   // tensor i's word of amax, -1 = none
+    double *total;                    // += the pre-clip norm (nullable)
+};
 hipError_t launch_clip_adam(int n, float *const *params, float *const *grads, float *const *exp_avg,
                             float *const *exp_avg_sq, float *const *steps, const int64_t *numel, double lr, double beta1,
-                            double beta2, double eps, float max_norm, float *norm_out, double *partial, hipStream_t s);
+                            double beta2, double eps, float max_norm, float *norm_out, double *partial, hipStream_t s,
+                            const struct OptChain *chain = nullptr);
 
 // few-shot evaluation's reductions (merlin_fewshot.hip): per-task clip_grad_norm_ + SGD over stacked parameter
 // sets float[G][numel[i]], and the per-episode GAE / normalisation / loss of [T][n] episodes

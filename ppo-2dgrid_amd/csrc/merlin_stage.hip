@@ -18,6 +18,11 @@
 // through LDS.  Every sum runs in a fixed order (the same bits every call) and accumulates in f64, rounded once to
 // f32 (dH, HT, T2 and the gradients): more accurate than the fp32 blocked sums of the torch formulation
 // (tests/test_gpu_stage_precision.py), for ~11 M multiply-adds per table, where the f64 rate costs nothing visible.
+//
+// The fast step's weight-only chain (merlin/fast_step.py NATIVE_CHAIN) uses two launches that carry a neighbour's work
+// as extra block ranges, with the same bits: k_stage_fwd_planes (the forward's blocks, then the h3 plane splits of
+// fc1's weight and its transpose) and k_stage_fold_scatter (k_stage_fold's blocks, then the scatter of the derived
+// gradients onto the flat gradient buffer).
 #include "merlin_internal.h"
 
 namespace merlin {
@@ -58,16 +63,15 @@ __device__ void load_w2_slice_co(const float *__restrict__ W2, int p, float *__r
     }
 }
 
-// grid (NCH, T): HT rows of one chunk and their T2 rows; HT saved for the backward
-__global__ __launch_bounds__(256) void k_stage_fwd(const float *__restrict__ W1, const float *__restrict__ b1,
-                                                   const float *__restrict__ W2, const float *__restrict__ atlas,
-                                                   const int16_t *__restrict__ idx, float *__restrict__ HT,
-                                                   float *__restrict__ T2) {
+// one block (256 threads) of the forward: tower t's HT rows of one chunk and their T2 rows; HT saved for the backward
+__device__ __forceinline__ void stage_fwd_block(int chunk, int t, const float *__restrict__ W1,
+                                                const float *__restrict__ b1, const float *__restrict__ W2,
+                                                const float *__restrict__ atlas, const int16_t *__restrict__ idx,
+                                                float *__restrict__ HT, float *__restrict__ T2) {
     __shared__ float Wl[C1 * 3 * 64], Al[5 * 3 * 64], H[VB][C1], Ws[4 * C1 * WSP];
     __shared__ double P[C1 * 80];
-    const int t = blockIdx.y;
     int p, v0, nv;
-    chunk_of(blockIdx.x, p, v0, nv);
+    chunk_of(chunk, p, v0, nv);
     W1 += (size_t)t * C1 * 3 * 64;
     for (int q = threadIdx.x; q < C1 * 3 * 64; q += 256) Wl[q] = W1[q];
     for (int q = threadIdx.x; q < 5 * 3 * 64; q += 256) Al[q] = atlas[q];
@@ -108,6 +112,50 @@ __global__ __launch_bounds__(256) void k_stage_fwd(const float *__restrict__ W1,
 #pragma unroll 8
         for (int o = 0; o < C1; o++) acc += (double)H[vl][o] * (double)w[o * WSP];
         T2[((size_t)t * NROW + 4 * (v0 + vl) + j) * C2 + co] = (float)acc;
+    }
+}
+
+// grid (NCH, T)
+__global__ __launch_bounds__(256) void k_stage_fwd(const float *__restrict__ W1, const float *__restrict__ b1,
+                                                   const float *__restrict__ W2, const float *__restrict__ atlas,
+                                                   const int16_t *__restrict__ idx, float *__restrict__ HT,
+                                                   float *__restrict__ T2) {
+    stage_fwd_block(blockIdx.x, blockIdx.y, W1, b1, W2, atlas, idx, HT, T2);
+}
+
+// The forward and fc1's weight planes as block ranges of one launch (the fast step's weight-only chain):
+// blocks [0, NCH * T): k_stage_fwd's blocks; then SPLIT_BLK blocks per (tensor, tower) that split x[which][t]
+// (W4p, W4p^T: [T][8 g8] fp32 each) into its h3 planes at the scale amax[t] -- csrc/merlin_h3.hip's k_h3_split, the
+// same expressions (h3_pair) on the same values.  The table blocks come first and run ~20 us on their own CUs; the
+// split blocks are few enough to fit beside them (a block of this kernel holds half a CU's LDS).
+constexpr int SPLIT_BLK = 20;
+__global__ __launch_bounds__(256) void k_stage_fwd_planes(const float *__restrict__ W1, const float *__restrict__ b1,
+                                                          const float *__restrict__ W2,
+                                                          const float *__restrict__ atlas,
+                                                          const int16_t *__restrict__ idx, int T,
+                                                          float *__restrict__ HT, float *__restrict__ T2,
+                                                          const float4 *__restrict__ x0, const float4 *__restrict__ x1,
+                                                          int64_t g8, const uint32_t *amax, uint4 *__restrict__ pl0,
+                                                          uint4 *__restrict__ pl1) {
+    const int nst = NCH * T;
+    if ((int)blockIdx.x < nst) {
+        stage_fwd_block(blockIdx.x % NCH, blockIdx.x / NCH, W1, b1, W2, atlas, idx, HT, T2);
+        return;
+    }
+    const int b = blockIdx.x - nst, job = b / SPLIT_BLK, r = b - job * SPLIT_BLK, which = job / T, t = job - which * T;
+    const int e = h3_exp(load_amax(amax + t));
+    const float sc = pow2f(e), sc2 = pow2f(e + 11);
+    const float4 *__restrict__ x = (which ? x1 : x0) + t * g8 * 2;
+    uint4 *__restrict__ pl = (which ? pl1 : pl0) + t * g8 * 2;
+    for (int64_t q = (int64_t)r * 256 + threadIdx.x; q < g8; q += SPLIT_BLK * 256) {
+        const float4 a = x[2 * q], c = x[2 * q + 1];
+        uint32_t h0, h1, h2, h3, l0, l1, l2, l3;
+        h3_pair(a.x, a.y, sc, sc2, h0, l0);
+        h3_pair(a.z, a.w, sc, sc2, h1, l1);
+        h3_pair(c.x, c.y, sc, sc2, h2, l2);
+        h3_pair(c.z, c.w, sc, sc2, h3, l3);
+        pl[2 * q] = make_uint4(h0, h1, h2, h3);
+        pl[2 * q + 1] = make_uint4(l0, l1, l2, l3);
     }
 }
 
@@ -272,11 +320,80 @@ __global__ __launch_bounds__(256) void k_stage_fold(const double *__restrict__ w
     }
 }
 
+// k_stage_fold's blocks, then the scatter of the derived-gradient buffer onto the flat gradient in the same launch
+// (flat[map[i]] = DG[i], i < n: torch's index_copy_ before).  blocks [0, T * 4): type 3's dW2 at tap j as in
+// k_stage_fold, written to DG and straight to its mapped slots; blocks from T * 4: SC_CHUNK elements of DG each,
+// every segment but those taps (tap & 5 == 5 of the dW2 segment at w2), which are complete before this launch.
+constexpr int SC_CHUNK = 1024;
+__global__ __launch_bounds__(256) void k_stage_fold_scatter(const double *__restrict__ ws, float *DG, int64_t w2, int T,
+                                                            const int32_t *__restrict__ map, int64_t n,
+                                                            float *__restrict__ flat) {
+    if ((int)blockIdx.x < T * 4) {
+        const int t = blockIdx.x >> 2, j = blockIdx.x & 3, l = threadIdx.x, o = l & (C1 - 1), cq = l >> 5;
+        const int tap = (2 * (j >> 1) + 1) * 4 + 2 * (j & 1) + 1;
+        const double *w = ws + ((size_t)t * 4 + j) * NP3 * 2048;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            double s = w[i * 256 + l];
+            for (int q = 1; q < NP3; q++) s += w[q * 2048 + i * 256 + l];
+            const int64_t d = w2 + (((int64_t)t * C2 + cq + 8 * i) * C1 + o) * 16 + tap;
+            DG[d] = (float)s;
+            flat[map[d]] = (float)s;
+        }
+        return;
+    }
+    const int64_t base = (int64_t)(blockIdx.x - T * 4) * SC_CHUNK, w2e = w2 + (int64_t)T * C2 * C1 * 16;
+#pragma unroll
+    for (int k = 0; k < SC_CHUNK / 256; k++) {
+        const int64_t i = base + k * 256 + threadIdx.x;
+        if (i < n && !(i >= w2 && i < w2e && ((i - w2) & 5) == 5)) flat[map[i]] = DG[i];
+    }
+}
+
+// dst[i] = src[map[i]], i < n (the derived-weight buffer from the flat parameters: torch's index_select before)
+__global__ __launch_bounds__(256) void k_stage_gather(const float *__restrict__ src, const int32_t *__restrict__ map,
+                                                      int64_t n, float *__restrict__ dst) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = src[map[i]];
+}
+
 }  // namespace
 
 hipError_t launch_stage_fwd(const float *W1, const float *b1, const float *W2, const float *atlas, const int16_t *idx,
                             int T, float *HT, float *T2, hipStream_t s) {
     hipLaunchKernelGGL(k_stage_fwd, dim3(NCH, T), dim3(256), 0, s, W1, b1, W2, atlas, idx, HT, T2);
+    return hipGetLastError();
+}
+
+hipError_t launch_stage_fwd_planes(const float *W1, const float *b1, const float *W2, const float *atlas,
+                                   const int16_t *idx, int T, float *HT, float *T2, const float *x0, const float *x1,
+                                   int64_t n, const uint32_t *amax, void *planes0, void *planes1, hipStream_t s) {
+    const int split = x0 ? 2 * T * SPLIT_BLK : 0;
+    hipLaunchKernelGGL(k_stage_fwd_planes, dim3(NCH * T + split), dim3(256), 0, s, W1, b1, W2, atlas, idx, T, HT, T2,
+                       reinterpret_cast<const float4 *>(x0), reinterpret_cast<const float4 *>(x1), n / 8, amax,
+                       static_cast<uint4 *>(planes0), static_cast<uint4 *>(planes1));
+    return hipGetLastError();
+}
+
+hipError_t launch_stage_gather(const float *src, const int32_t *map, int64_t n, float *dst, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_stage_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, map, n, dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_stage_bwd_scatter(const float *W2, const float *HT, const float *dT2, const float *atlas,
+                                    const int16_t *koff, const int16_t *kv, int T, float *dH, float *DG, int64_t w1,
+                                    int64_t b1, int64_t w2, const int32_t *map, int64_t n, float *flat, double *ws,
+                                    hipStream_t s) {
+    hipLaunchKernelGGL(k_stage_bwd_h, dim3(NCH, T), dim3(256), 0, s, W2, HT, dT2, dH);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_stage_bwd_w, dim3(T * NI + T * C1), dim3(WT), 0, s, HT, dT2, dH, atlas, koff, kv, T, DG + w1,
+                       DG + b1, DG + w2, ws);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const unsigned blocks = (unsigned)(T * 4 + (n + SC_CHUNK - 1) / SC_CHUNK);
+    hipLaunchKernelGGL(k_stage_fold_scatter, dim3(blocks), dim3(256), 0, s, (const double *)ws, DG, w2, T, map, n, flat);
     return hipGetLastError();
 }
 

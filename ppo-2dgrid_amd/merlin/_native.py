@@ -178,6 +178,11 @@ def lib():
     L.merlin_act_draw.argtypes = [vp, i32, i64, vp, vp, i32, i32, C.c_uint64, vp, i64, i64, vp, vp, vp, vp]
     L.merlin_stage_tables_fwd.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
     L.merlin_stage_tables_bwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.merlin_stage_fwd_planes.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp]
+    L.merlin_stage_bwd_scatter.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, i64, i64, i64, vp, i64, vp, vp]
+    L.merlin_gather_f32.argtypes = [vp, vp, i64, vp, vp]
+    L.merlin_clip_adam_chain.argtypes = [i32, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double,
+                                         C.c_float, vp, vp, vp, i32, vp, i32, vp, i64, vp, vp, vp, vp, vp, vp]
     L.merlin_window_gemm_fwd.argtypes = [vp, vp, i32, i64, vp, vp]
     L.merlin_window_gemm_bwd_work.argtypes = [i32, i64]
     L.merlin_window_gemm_bwd_work.restype = i64
@@ -238,7 +243,8 @@ EXPORTED_SYMBOLS = (
     "merlin_tower_colsum",
     "merlin_ppo_loss_workspace", "merlin_ppo_loss", "merlin_act_heads",
     "merlin_x6_split", "merlin_x6_join", "merlin_x6_gemm_nt", "merlin_x6_tn_slab_floats", "merlin_x6_gemm_tn",
-    "merlin_clip_adam_workspace", "merlin_clip_adam",
+    "merlin_clip_adam_workspace", "merlin_clip_adam", "merlin_clip_adam_chain",
+    "merlin_stage_fwd_planes", "merlin_stage_bwd_scatter", "merlin_gather_f32",
     "merlin_h3_amax", "merlin_h3_split", "merlin_h3_gemm_nt", "merlin_h3_gemm_tn",
     "merlin_h3_gemm_tn_planes", "merlin_h3_gemm_nt_gather", "merlin_h3_gemm_tn_gather",
     "merlin_h3_gemm_nt_heads", "merlin_h3_heads_parts", "merlin_heads_combine", "merlin_act_draw",
@@ -1684,8 +1690,64 @@ def stage_tables_bwd(W2, HT, dT2, atlas, koff, kv, dW1=None, db1=None, dW2=None,
     return dW1, db1, dW2
 
 
+def stage_fwd_planes(W1, b1, W2, atlas, idx, HT, T2, x0=None, x1=None, amax=None, planes0=None, planes1=None):
+    """stage_tables_fwd into HT / T2 and, with x0 / x1 (f32 [T, ...] of equal size), h3_split(x0, amax) into planes0
+    and h3_split(x1, amax) into planes1, as block ranges of one launch (merlin_stage_fwd_planes): the same bits."""
+    T = int(W1.shape[0])
+    assert W1.shape == (T, 32, 3, 8, 8) and b1.shape == (T, 32) and W2.shape == (T, 64, 32, 4, 4)
+    assert all(x.dtype == torch.float32 and x.is_contiguous() for x in (W1, b1, W2, atlas, HT, T2))
+    assert idx.dtype == torch.int16 and idx.shape == (680, 4) and atlas.shape == (5, 3, 8, 8)
+    assert HT.shape == (T, 680, 32) and T2.shape == (T, LUT2_ROWS, 64)
+    n = 0
+    if x0 is not None:
+        n = x0.numel() // T
+        assert x0.shape[0] == x1.shape[0] == T and x0.numel() == x1.numel() == n * T and n % 8 == 0
+        assert x0.dtype == x1.dtype == torch.float32 and x0.is_contiguous() and x1.is_contiguous()
+        assert amax.dtype == torch.int32 and amax.numel() >= T
+        for pl in (planes0, planes1):
+            assert pl.dtype == torch.int16 and pl.numel() == 2 * n * T and pl.is_contiguous()
+    check(lib().merlin_stage_fwd_planes(ptr(W1), ptr(b1), ptr(W2), ptr(atlas), ptr(idx), T, ptr(HT), ptr(T2), ptr(x0),
+                                        ptr(x1), n, ptr(amax), ptr(planes0), ptr(planes1), stream_of(W1)),
+          "merlin_stage_fwd_planes")
+    return HT, T2
+
+
+def stage_bwd_scatter(W2, HT, dT2, atlas, koff, kv, dH, DG, off_w1, off_b1, off_w2, fmap, n, flat):
+    """stage_tables_bwd with dW1 / db1 / dW2 at their offsets of the derived-gradient buffer DG, and in the same three
+    launches flat[fmap[i]] = DG[i] for i < n (fmap int32, distinct: flat.index_copy_(0, fmap[:n], DG[:n]))."""
+    T = int(W2.shape[0])
+    assert dT2.shape == (T, LUT2_ROWS, 64) and HT.shape == (T, 680, 32) and dH.shape == (T, 680, 32)
+    assert all(x.dtype == torch.float32 and x.is_contiguous() for x in (W2, HT, dT2, dH, DG, flat, atlas))
+    assert koff.dtype == kv.dtype == torch.int16 and koff.numel() == 81 and kv.numel() == 2720
+    assert fmap.dtype == torch.int32 and fmap.is_contiguous() and 0 <= n <= min(fmap.numel(), DG.numel())
+    check(lib().merlin_stage_bwd_scatter(ptr(W2), ptr(HT), ptr(dT2), ptr(atlas), ptr(koff), ptr(kv), T, ptr(dH),
+                                         ptr(DG), int(off_w1), int(off_b1), int(off_w2), ptr(fmap), int(n), ptr(flat),
+                                         stream_of(W2)), "merlin_stage_bwd_scatter")
+
+
+def gather_f32(src, fmap, out):
+    """out[i] = src[fmap[i]] (fmap int32 [out.numel()]): src.index_select(0, fmap) in one native launch."""
+    assert src.dtype == out.dtype == torch.float32 and fmap.dtype == torch.int32
+    assert src.is_contiguous() and out.is_contiguous() and fmap.is_contiguous() and fmap.numel() == out.numel()
+    check(lib().merlin_gather_f32(ptr(src), ptr(fmap), out.numel(), ptr(out), stream_of(src)), "merlin_gather_f32")
+    return out
+
+
+class AdamChain:
+    """What merlin_clip_adam_chain's two launches take over in the fast step's weight-only chain: word lists to zero
+    (int32 tensors), the flat parameter buffer, each of its elements' slots int32 [n_flat, 2] in the derived-weight
+    buffer D, scale words amax with the tensors folded into them ({id(param): word}), and total f64[1] += norm."""
+
+    def __init__(self, zero, flat, slots, D, amax=None, amax_slot=None, total=None):
+        assert len(zero) <= 2 and all(z.dtype == torch.int32 and z.is_contiguous() for z in zero)
+        assert flat.dtype == D.dtype == torch.float32 and flat.is_contiguous() and D.is_contiguous()
+        assert slots.dtype == torch.int32 and slots.shape == (flat.numel(), 2) and slots.is_contiguous()
+        self.zero, self.flat, self.slots, self.D = list(zero), flat, slots, D
+        self.amax, self.amax_slot, self.total = amax, dict(amax_slot or {}), total
+
+
 def clip_adam(params, grads, exp_avgs, exp_avg_sqs, steps, lr, beta1, beta2, eps, max_norm, norm_out=None,
-              workspace=None):
+              workspace=None, chain=None):
     """clip_grad_norm_(params, max_norm) + torch's fused Adam step (src/ppo.py:153-156) in two
     launches (merlin_clip_adam): the gradients are clipped in place, (param, exp_avg, exp_avg_sq)
     updated, each float32[1] step counter advanced (a zero-element tensor's too, as torch's Adam does).  Returns
@@ -1702,6 +1764,8 @@ def clip_adam(params, grads, exp_avgs, exp_avg_sqs, steps, lr, beta1, beta2, eps
             raise ValueError("clip_adam: a parameter and its gradient / state differ in size")
     if n > 32:
         raise ValueError("clip_adam: at most 32 tensors")
+    if chain is not None and any(p.numel() == 0 for p in params):
+        raise ValueError("clip_adam: the chained form takes tensors with elements only")
     if any(p.numel() == 0 for p in params):
         # a tensor without elements adds nothing to the norm and has nothing to update, but torch's Adam still
         # advances its step counter; merlin_clip_adam takes numel > 0 only, so it gets the other tensors
@@ -1722,6 +1786,19 @@ def clip_adam(params, grads, exp_avgs, exp_avg_sqs, steps, lr, beta1, beta2, eps
         workspace = torch.empty(int(lib().merlin_clip_adam_workspace(n, numel)), dtype=torch.float64, device=dev)
     if norm_out is None:
         norm_out = torch.empty((), dtype=torch.float32, device=dev)
+    if chain is not None:  # the same two launches with their neighbours' work (AdamChain)
+        z = chain.zero + [None] * (2 - len(chain.zero))
+        slot = (C.c_int32 * n)(*[int(chain.amax_slot.get(id(p), -1)) for p in params]) if chain.amax_slot else None
+        tot = chain.total
+        assert tot is None or (tot.dtype == torch.float64 and tot.numel() == 1)
+        check(lib().merlin_clip_adam_chain(n, arr(params), arr(grads), arr(exp_avgs), arr(exp_avg_sqs), arr(steps),
+                                           numel, float(lr), float(beta1), float(beta2), float(eps), float(max_norm),
+                                           ptr(norm_out), ptr(workspace), ptr(z[0]),
+                                           0 if z[0] is None else z[0].numel(), ptr(z[1]),
+                                           0 if z[1] is None else z[1].numel(), ptr(chain.flat), chain.flat.numel(),
+                                           ptr(chain.slots), ptr(chain.D), ptr(chain.amax), slot, ptr(tot),
+                                           stream_of(params[0])), "merlin_clip_adam_chain")
+        return norm_out
     check(lib().merlin_clip_adam(n, arr(params), arr(grads), arr(exp_avgs), arr(exp_avg_sqs), arr(steps), numel,
                                  float(lr), float(beta1), float(beta2), float(eps), float(max_norm), ptr(norm_out),
                                  ptr(workspace), stream_of(params[0])), "merlin_clip_adam")

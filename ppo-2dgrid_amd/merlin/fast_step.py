@@ -11,7 +11,9 @@ Here the step is the same kernels with the same operands in the same order, issu
     input gradient) is one captured HIP graph, and the backward of that subgraph (the table / stacking
     adjoints down to every parameter's gradient, written into a flat gradient buffer) a second one.
     Parameters keep their storage for the whole run (the optimizer updates them in place), so the
-    graphs replay on live weights.
+    graphs replay on live weights.  With NATIVE_CHAIN (the default for the HIP tables) there is no graph: the
+    stage's backward, clip + Adam and the stage's forward are six plain launches of the library, which also
+    do what torch's index_copy_ / index_select, the scale reductions, the plane splits and the zeroings did.
   * the per-minibatch bookkeeping (slot / inv / order / offs / live-patch maps) comes as views of
     update-wide arrays (WindowPlan.update_minibatches(bulk=True)): no launches of its own.
   * the data-dependent part (window tables, conv3, fc1, heads, loss, their backward passes, conv3's
@@ -99,7 +101,12 @@ class WeightStage:
         self.fwd_map = torch.cat([t.reshape(-1) for _, t in segs]).to(dev)
         self.n_grad = self.offs["W4pT"]  # every stage-parameter element once in D[:n_grad]
         assert int(self.fwd_map[:self.n_grad].unique().numel()) == self.n_grad
-        self._capture()
+        # the weight-only chain as plain native launches (NATIVE_CHAIN) instead of the two graphs
+        self.native = native_chain(impl)
+        if self.native:
+            self._alloc_native()
+        else:
+            self._capture()
 
     def seg(self, buf, name):
         o = self.offs[name]
@@ -132,6 +139,72 @@ class WeightStage:
         planes = nat.x6_split(D[o:self.offs["W3rT"]].view(-1, 8)).view(-1)  # W4p and W4p^T back to back
         n4 = 2 * H * 576 * 3
         return D, leaves, T2, (planes[:n4].view(2, H, 3 * 576), planes[n4:].view(2, 576, 3 * H))
+
+    def _alloc_native(self):
+        """The chain's buffers, kept for the stage's life (no graph, nothing allocated per step): D and DG, the
+        tables, fc1's weight planes, fwd_map as int32 and its inverse -- each flat element's slots of D."""
+        dev = self.flat_params.device
+        n, nf = self.fwd_map.numel(), self.flat_params.numel()
+        assert max(n, nf) < 2 ** 31
+        self.map32 = self.fwd_map.to(torch.int32)
+        cnt = torch.bincount(self.fwd_map, minlength=nf)
+        assert int(cnt.max()) <= 2  # fc1's and conv3's weights appear straight and transposed, the rest once
+        order = torch.argsort(self.fwd_map, stable=True)  # D slots by flat element: a CSR with rows of <= 2
+        first = torch.cumsum(cnt, 0) - cnt
+        slots = torch.full((nf, 2), -1, dtype=torch.int32, device=dev)
+        for k in range(2):
+            has = cnt > k
+            slots[has, k] = order[first[has] + k].to(torch.int32)
+        self.slots = slots
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.D, self.DG = torch.zeros(n, **f32), torch.zeros(n, **f32)
+        self.gT2 = torch.zeros((2, nat.LUT2_ROWS, 64), **f32)
+        self._dH, self.HT = torch.empty((2, 680, 32), **f32), torch.empty((2, 680, 32), **f32)
+        self.T2 = torch.empty((2, nat.LUT2_ROWS, 64), **f32)
+        H = self.shapes["W4p"][1]
+        self.planes = ()
+        if self.fc1 == "h3":
+            self._p4 = (torch.empty((2, H, 1152), dtype=torch.int16, device=dev),
+                        torch.empty((2, 576, 2 * H), dtype=torch.int16, device=dev))
+            self.planes = self._p4
+        self.outs = (self.T2,) + tuple(self.seg(self.D, k) for k in ("b2", "W3r", "b3", "W4p", "b4"))
+        self.grads = (self.gT2,) + tuple(self.seg(self.DG, k) for k in ("b2", "W3r", "b3", "W4p", "b4"))
+        self.refresh()
+
+    def refresh(self):
+        """D and fc1's weight scale from the parameters as they are now (the chained Adam keeps both current from
+        step to step inside an update; a checkpoint load, a broadcast or an in-place edit between updates does not
+        pass through it)."""
+        nat.gather_f32(self.flat_params, self.map32, self.D)
+        if self.fc1 == "h3":
+            nat.h3_amax(self.seg(self.D, "W4p"), out=self.amaxW)
+
+    def _fwd_native(self):
+        D = self.D
+        W1, b1, W2 = (self.seg(D, k) for k in ("W1", "b1", "W2"))
+        atlas, idx = self.ac.stage_consts(D.device)[:2]
+        if self.fc1 == "h3":  # the tables and W4p's / W4p^T's planes (amaxW is final once Adam has ended): one launch
+            nat.stage_fwd_planes(W1, b1, W2, atlas, idx, self.HT, self.T2, self.seg(D, "W4p"), self.seg(D, "W4pT"),
+                                 self.amaxW, *self._p4)
+            planes = self._p4
+            if WINDOW_H3:
+                W3r, W3rT = self.seg(D, "W3r"), self.seg(D, "W3rT")
+                nat.h3_amax(W3r, out=self.amaxW3)
+                planes += (nat.h3_split(W3rT, self.amaxW3), nat.h3_split(W3r, self.amaxW3))
+            self.planes = planes
+        else:
+            nat.stage_fwd_planes(W1, b1, W2, atlas, idx, self.HT, self.T2)
+            o, H = self.offs["W4p"], self.shapes["W4p"][1]
+            planes = nat.x6_split(D[o:self.offs["W3rT"]].view(-1, 8)).view(-1)  # W4p and W4p^T back to back
+            n4 = 2 * H * 576 * 3
+            self.planes = (planes[:n4].view(2, H, 3 * 576), planes[n4:].view(2, 576, 3 * H))
+        return self.outs
+
+    def _bwd_native(self):
+        atlas, _, koff, kv = self.ac.stage_consts(self.DG.device)
+        nat.stage_bwd_scatter(self.seg(self.D, "W2"), self.HT, self.gT2, atlas, koff, kv, self._dH, self.DG,
+                              self.offs["W1"], self.offs["b1"], self.offs["W2"], self.map32, self.n_grad,
+                              self.flat_grad)
 
     def _capture(self):
         main = torch.cuda.current_stream()
@@ -177,11 +250,29 @@ class WeightStage:
         return self.flat_params.data_ptr() == self.ptr
 
     def forward(self):
+        if self.native:
+            return self._fwd_native()
         self.gfwd.replay()
         return self.outs
 
     def backward(self):
+        if self.native:
+            return self._bwd_native()
         self.gbwd.replay()
+
+
+# The weight-only chain of the optimizer step -- the stage's backward, clip + Adam, the stage's forward -- as six plain
+# launches of the library (WeightStage._bwd_native / _fwd_native, merlin_clip_adam_chain): no graph replay, no torch
+# kernel.  The scatter onto the flat gradient rides in k_stage_fold's launch; Adam's two launches write the derived
+# weights D and fc1's weight scale beside the parameters, zero the next step's operand scales and add the norm to the
+# update's total; fc1's weight planes are block ranges of k_stage_fwd's launch.  Same bits
+# (tests/test_gpu_native_chain.py).  False, and with stage_impl "torch": the two captured graphs and the launches
+# around them (index_copy_, index_select, h3_amax, two h3_split, two zeroings, the norm's add).
+NATIVE_CHAIN = True
+
+
+def native_chain(stage_impl: str) -> bool:
+    return bool(NATIVE_CHAIN) and stage_impl == "hip"
 
 
 # fc1's weight gradient on the side stream from right after the heads' backward (True: beside the input gradient
@@ -281,9 +372,18 @@ class WindowStep:
         # [0:2] max |a3|, [2:4] max |dz| (or its bound), [4:13] the loss's max |dlogits[:, j]| / |dvalue| (DZ_PLANES)
         self.amax_act = torch.zeros(16, dtype=torch.int32, device=agent.device)
         self.amax_win = torch.zeros(4, dtype=torch.int32, device=agent.device)  # a2w's and dQ's scales
+        self.chain = None
+        if self.stage.native:  # what clip + Adam's launches do for the chain (merlin/optim.py ClipAdam.chain)
+            h3 = self.fc1 == "h3"
+            fa, fc = ac.actor[0].weight, ac.critic[0].weight
+            self.chain = nat.AdamChain([self.amax_act, self.stage.amaxW] if h3 else [], flat_params, self.stage.slots,
+                                       self.stage.D, amax=self.stage.amaxW if h3 else None,
+                                       amax_slot={id(fa): 0, id(fc): 1} if h3 else None)
 
     def valid(self) -> bool:
         if not (self.stage.valid() and all(p.requires_grad for p in self.params)):
+            return False
+        if self.stage.native != native_chain(self.stage.impl):  # NATIVE_CHAIN was switched: another stage
             return False
         ag = self._agent()
         if ag is None or getattr(ag.ac, "fc1_impl", "h3") != self.fc1:
@@ -296,11 +396,27 @@ class WindowStep:
         return True
 
     def bind_grads(self):
-        """Every parameter's .grad is its view of the flat buffer (each step overwrites all of them)."""
+        """Every parameter's .grad is its view of the flat buffer (each step overwrites all of them).  Once per
+        update; with the native chain the derived weights are read afresh from the parameters here."""
         for p in self.params:
             v = self.views[p]
             if p.grad is None or p.grad.data_ptr() != v.data_ptr():
                 p.grad = v
+        if self.stage.native:
+            self.refresh()
+
+    def refresh(self):
+        """Native chain: the derived weights and fc1's weight scale from the parameters as they are, the step's
+        operand scales zeroed -- what the chained Adam launches leave behind after every step of an update."""
+        self.stage.refresh()
+        if self.fc1 == "h3":
+            self.amax_act.zero_()
+
+    def begin_update(self, totals):
+        """The chain for this update's clip + Adam launches (None: the graphs' form), its norm total totals[5]."""
+        if self.chain is not None:
+            self.chain.total = totals[5:]
+        return self.chain
 
     def side_stream(self, device):
         key = (SIDE_PRIORITY, SIDE_CU_GROUPS)
@@ -328,8 +444,14 @@ class WindowStep:
             self._step(plan, mb, mb_idx, actions, logp_old, adv, ret, totals)
         cur.wait_stream(hp)
 
+    def _on(self, side):
+        """The side stream as the current one, noting that this step queued work on it."""
+        self._side_used = True
+        return torch.cuda.stream(side)
+
     def _step(self, plan, mb, mb_idx, actions, logp_old, adv, ret, totals):
         ag = self._agent()
+        self._side_used = False
         Wa, ba, Wc, bc = self.head
         g = self.stage.grads  # (dT2, db2, dW3r, db3, dW4p, db4)
         # ---- forward (merlin/windows.py window_tower_head_x6)
@@ -339,7 +461,7 @@ class WindowStep:
         # memset node replays with a wrong fill value on ROCm 7 (0x80808080: an exponent that overflows every plane,
         # NaN in the second update; scripts/probe_graph_then.py)
         am = self.amax_act
-        if h3:
+        if h3 and not self.stage.native:  # (native chain: zeroed by the preceding step's k_opt_sumsq, or refresh())
             am.zero_()
         T2, b2, W3r, b3, _, b4 = self.stage.forward()
         P4, P4t = self.stage.planes[:2]
@@ -381,7 +503,7 @@ class WindowStep:
         masks_ready = None
         if arows is not None and MASK_COPY_SIDE and not MASK_ROWS:
             side.wait_stream(main)
-            with torch.cuda.stream(side):
+            with self._on(side):
                 nat.window_conv3_copy_masks(Y3, bits, rep_row)
                 masks_ready = torch.cuda.Event()
                 masks_ready.record(side)
@@ -389,7 +511,7 @@ class WindowStep:
             Y3.record_stream(side)
         if split_side:  # a3's planes for the weight gradient, on the side stream beside the forward GEMM
             side.wait_stream(main)
-            with torch.cuda.stream(side):
+            with self._on(side):
                 pa3 = nat.h3_split(a3, am3)
         if h3:
             # the forward and input-gradient GEMMs leave their fp32 operand's planes (a3's, dz's) for the weight
@@ -423,7 +545,7 @@ class WindowStep:
                                    out_w_critic=self.views[Wc], amax=amz if h3 else None, grad_absmax=dmax)
         if split_side:  # and dz's beside the input-gradient GEMM
             side.wait_stream(main)
-            with torch.cuda.stream(side):
+            with self._on(side):
                 pdz = nat.h3_split(dz, amz)
 
         def wgrad():
@@ -437,7 +559,7 @@ class WindowStep:
 
         if WGRAD_EARLY:  # fc1's weight gradient beside the input gradient and conv3's segmented sums
             side.wait_stream(main)
-            with torch.cuda.stream(side):
+            with self._on(side):
                 wgrad()
         # conv3's backward chain's fills (the band marks preset to -1, the dQ table zeroed) ahead of the side-stream
         # weight gradient: launched beside it, a small fill waits for a CU the GEMM's blocks free (~90 us each with
@@ -456,7 +578,7 @@ class WindowStep:
             wgrad()
         elif not WGRAD_EARLY:  # fc1's weight gradient beside conv3's segmented sums
             side.wait_stream(main)
-            with torch.cuda.stream(side):
+            with self._on(side):
                 wgrad()
         for x in (dz, a3, pdz, pa3):
             if x is not None:
@@ -481,7 +603,8 @@ class WindowStep:
         if wh3 or not WINDOW_BWD_HIP:
             nat.relu_bwd(a2w, da2w, out=da2w, out_bias=g[1])
         nat.segment_sum(da2w, plan.hist, nat.LUT2_ROWS, name="k_seg_sum_dT2", out=g[0])
-        main.wait_stream(side)
+        if self._side_used:  # (the wait on an idle stream still costs the main stream ~6 us in front of the chain)
+            main.wait_stream(side)
         self.stage.backward()
 
 

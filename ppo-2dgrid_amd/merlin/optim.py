@@ -27,6 +27,9 @@ class ClipAdam:
         self.max_norm = float(max_norm)
         self._ws = None
         self._norm = None
+        # merlin._native.AdamChain or None: the fast step's weight-only chain rides in the same two launches
+        # (merlin/fast_step.py NATIVE_CHAIN; set by PPO._sgd for the update it is running)
+        self.chain = None
 
     def step(self) -> torch.Tensor:
         """clip_grad_norm_(params, max_norm) then Adam.step(); returns the pre-clip norm (0-d f32)."""
@@ -53,4 +56,4 @@ class ClipAdam:
             lr = float(lr)
         return nat.clip_adam(ps, [p.grad for p in ps], [st[p]["exp_avg"] for p in ps],
                              [st[p]["exp_avg_sq"] for p in ps], [st[p]["step"] for p in ps], lr, b1, b2, g["eps"],
-                             self.max_norm, norm_out=self._norm, workspace=self._ws)
+                             self.max_norm, norm_out=self._norm, workspace=self._ws, chain=self.chain)

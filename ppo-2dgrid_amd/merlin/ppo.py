@@ -555,6 +555,11 @@ class PPO:
                     self._rehome_parameters()
                 self._wstep = WindowStep(self)
             self._wstep.bind_grads()
+        # the fast step's weight-only chain (merlin/fast_step.py NATIVE_CHAIN): clip + Adam's two launches also keep
+        # the derived weights and fc1's weight scale current, zero the next step's operand scales and add the norm
+        chain = self._wstep.begin_update(totals) if fast else None
+        if self._clip_adam is not None:
+            self._clip_adam.chain = chain
         # one host read per update for every minibatch's distinct-frame groups (merlin/windows.py)
         all_mbws = plan.update_minibatches(perms, self.minibatch_size, bulk=fast) if plan is not None else None
         for epoch in range(self.update_epochs):
@@ -608,9 +613,14 @@ class PPO:
                 else:
                     grad_norm = torch.nn.utils.clip_grad_norm_(self._params, 0.5)
                     self.optimizer.step()
-                totals[5:].add_(grad_norm.detach())
+                    if chain is not None:  # torch's optimizer stepped the parameters: the derived weights follow
+                        self._wstep.refresh()
+                if chain is None or self._clip_adam is None:  # (else added by the chained Adam launch)
+                    totals[5:].add_(grad_norm.detach())
                 nb += 1
                 host_mb.append(time.perf_counter())
+        if self._clip_adam is not None:
+            self._clip_adam.chain = None
         self.last_host_loop_ms = (time.perf_counter() - t_host) * 1e3  # host time to queue the update
         # host time to queue each minibatch's optimizer step (the first one includes the update's planning)
         self.last_host_mb_ms = [(b - a) * 1e3 for a, b in zip([t_host] + host_mb[:-1], host_mb)]

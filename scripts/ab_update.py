@@ -47,6 +47,7 @@ def main():
 
     clip_adam = agent._clip_adam
     host = {}
+    wsteps = {}
 
     def setter(name):
         def s():
@@ -61,6 +62,13 @@ def main():
             agent.fast_step = name.startswith("fast")  # merlin/fast_step.py vs the autograd engine
             from merlin import fast_step as FS
 
+            # the weight-only chain as six native launches ("nochain": the two graphs and the launches around them);
+            # each form keeps its WindowStep, so a switch does not rebuild the stage inside a timed update
+            chain = "nochain" not in name
+            if FS.NATIVE_CHAIN != chain:
+                wsteps[FS.NATIVE_CHAIN] = agent._wstep
+                FS.NATIVE_CHAIN = chain
+                agent._wstep = wsteps.get(chain)
             FS.WGRAD_EARLY = "wgrad_early" in name
             FS.SIDE_PRIORITY = -1 if "sidehi" in name else 0
             FS.SIDE_CU_GROUPS = next((int(t[2:]) for t in name.split("_") if t[:2] == "cu" and t[2:].isdigit()), 0)
