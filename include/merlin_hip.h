@@ -329,6 +329,53 @@ int merlin_policy_paths(const uint32_t *walls_dev, const int32_t *goal_dev, cons
  * marks in plain C++: the library's CPU-side restatement of the kernel. */
 int merlin_policy_paths_host(const uint32_t *walls, const int32_t *goal, const int8_t *action, int64_t n_maps,
                              int32_t size, int16_t *steps);
+/* The sampled-policy field (no reference counterpart).  A policy that SAMPLES its action from
+ * probabilities which depend on the view codes alone turns a map into a time-homogeneous Markov chain over its
+ * 4 size^2 poses; the two entries below are its dynamic programmes over the horizon, exact where a rollout is noisy.
+ * Dynamics: merlin_env_step's rule, unshaped (no StuckPenalty, no ExplorationBonus).  Action 0 turns left
+ * ((d + 3) & 3), 1 turns right ((d + 1) & 3), 2 moves forward: a front cell that is the goal terminates the episode,
+ * one that is a wall or off the grid leaves the pose unchanged (a self loop, not a dead end).  Action number t earns
+ * r_t = 1.0 - 0.9 * ((double)t / (double)T) if it terminates, and the episode is truncated after T = horizon actions.
+ * The goal cell is an ordinary free cell for a pose standing on it; a goal outside the grid: nothing terminates.
+ * probs_dev float32[n_maps][4][size][size][3], indexed [map][dir][y][x][action]; values at wall poses are ignored.
+ * The kernels widen to double and normalise, q_a = p_a / ((p_0 + p_1) + p_2) (float32 softmax rows do not sum to 1).
+ * A free pose whose row has a negative or non-finite entry or sums to zero is the caller's to keep out: not checked.
+ *
+ * Backwards: h_t(p) = the probability that an episode started in pose p at step count 0 terminates at exactly action t,
+ *   h_1(p) = q_F(p) [front(p) is the goal],  h_{t+1}(p) = (q_L(p) h_t(left p) + q_R(p) h_t(right p)) + q_F(p) g_t(p),
+ *   g_t(p) = 0 if front(p) is the goal, h_t(p) if it is a wall or off the grid, h_t(fwd p) otherwise.
+ * Outputs float64[n_maps][4][size][size], each nullable (not all), 8-B aligned, accumulated over t = 1..T:
+ *   success = sum h_t;  ret = sum h_t r_t;  steps = sum t h_t + T (1 - success), the expected episode length;
+ *   disc = sum h_t (G_t r_t), G_1 = 1, G_{t+1} = G_t gamma (a running product), the discounted return from step 0.
+ * Wall poses get NaN in all four.  size outside 5..32, horizon outside 1..16384, negative n_maps, a null input or all
+ * outputs null: MERLIN_E_INVALID; n_maps = 0 is a no-op.  One kernel, no allocation, no host sync: capturable. */
+int merlin_policy_chain(const uint32_t *walls_dev, const int32_t *goal_dev, const float *probs_dev, int64_t n_maps,
+                        int32_t size, int32_t horizon, double gamma, double *success_dev, double *ret_dev,
+                        double *steps_dev, double *disc_dev, void *stream);
+/* Forwards from one start pose per map, agent_dev int32[n_maps][4] = (x, y, dir, 0): mu_0 = the start pose, mu_{t+1}
+ * the chain's push-forward of mu_t, computed as a gather -- pose (x, y, d) receives mass from (x, y, (d + 1) & 3) by a
+ * left turn, from (x, y, (d + 3) & 3) by a right turn, from the free cell behind it by a forward move unless (x, y)
+ * is the goal, and from itself by a forward move if its front is blocked.
+ *   visits_dev float64[n_maps][4][size][size] = sum over t = 0..T-1 of mu_t, 0.0 at wall poses;
+ *   hit_dev float64[n_maps][T]: hit[m][t - 1] = the probability that the episode terminates at action t, summed over
+ *   the at most four poses facing the goal in the order d = 0..3.
+ * Each nullable (not both), 8-B aligned.  With the backward pass: sum_t hit = success[start], sum_t hit r_t =
+ * ret[start], sum_p visits = steps[start].  A start pose off the grid, on a wall or with dir outside 0..3 fills that
+ * map's outputs with NaN and raises MERLIN_DEVERR_BAD_FRAME (merlin_tower_errors), as merlin_view_codes does.
+ * Argument rules as merlin_policy_chain.  One kernel, no allocation, no host sync: capturable (after the device's
+ * first library call, which allocates the error word). */
+int merlin_policy_occupancy(const uint32_t *walls_dev, const int32_t *goal_dev, const float *probs_dev,
+                            const int32_t *agent_dev, int64_t n_maps, int32_t size, int32_t horizon,
+                            double *visits_dev, double *hit_dev, void *stream);
+/* [host] the two passes on host arrays by another route, a recursion / a scatter over an explicit successor table
+ * with three entries per pose and one absorbing state, in plain C++: the library's CPU-side restatements of the
+ * kernels.  An invalid start pose fills its map's outputs with NaN (there is no error word on the host). */
+int merlin_policy_chain_host(const uint32_t *walls, const int32_t *goal, const float *probs, int64_t n_maps,
+                             int32_t size, int32_t horizon, double gamma, double *success, double *ret,
+                             double *steps, double *disc);
+int merlin_policy_occupancy_host(const uint32_t *walls, const int32_t *goal, const float *probs,
+                                 const int32_t *agent, int64_t n_maps, int32_t size, int32_t horizon,
+                                 double *visits, double *hit);
 /* [sync] read-and-clear the device error bits and the fallback-map counter. */
 int merlin_env_errors(merlin_env *env, uint32_t *flags_host, uint32_t *fallbacks_host,
                       void *stream);

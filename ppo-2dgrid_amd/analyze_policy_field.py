@@ -12,6 +12,16 @@ map by map, and under "start" the start-pose view of the same tasks: the reward 
 each seed, predicted from the field, and the shortest path's length.  Unless --no_plots, the first --maps_to_draw maps
 of each difficulty are drawn to <out_dir>/<difficulty>_map<k>.png: the full-grid frame beside per-cell heatmaps of the
 least steps over the four directions, the number of trapped directions and the greatest value.
+
+    python ppo-2dgrid_amd/analyze_policy_field.py --model_path ppo.pth --difficulties medium --num_tasks 50 --sampled
+
+--sampled adds what the policy does when it SAMPLES its actions, as training does (merlin/sampled_field.py, DESIGN.md
+6f): per difficulty a "sampled" block with the metrics over all solvable poses (success rate, expected return and
+steps, the regret against the shortest path, the critic's error against the sampled discounted return), under "start"
+the probability of success and the expected reward and length of each seed's episode, and under
+"length_distribution" the episode-length distribution pooled over the seeds -- all exact, from two dynamic programmes
+over the policy's Markov chain, with no episode played.  Each drawn map then gains two heatmaps: the success
+probability (greatest over directions) and the expected visits per cell (summed over directions).
 """
 from __future__ import annotations
 
@@ -27,6 +37,7 @@ import torch  # noqa: E402
 
 from merlin.checkpoints import load_policy  # noqa: E402
 from merlin.policy_field import policy_field_for_seeds  # noqa: E402
+from merlin.sampled_field import sampled_field  # noqa: E402
 from merlin.scenario_creator import DEFAULT_CONFIG, ScenarioCreator  # noqa: E402
 from merlin.utils.utils import get_device  # noqa: E402
 
@@ -45,11 +56,27 @@ def parse_args(argv=None):
     p.add_argument("--out_dir", type=str, default="policy_field")
     p.add_argument("--no_plots", action="store_true")
     p.add_argument("--maps_to_draw", type=int, default=4, help="maps drawn per difficulty")
+    p.add_argument("--sampled", action="store_true",
+                   help="add the sampled policy's exact success / return / visits (merlin/sampled_field.py)")
     return p.parse_args(argv)
 
 
-def draw_maps(field, agent, name: str, k: int, out_dir: str) -> int:
-    """<out_dir>/<name>_map<i>.png for the first k maps; 0 when matplotlib is missing."""
+def sampled_block(sfield, agent, seeds):
+    """(the "sampled" block of one difficulty, visits float64[M, 4, S, S]) of a SampledField and the start poses."""
+    success, ret, steps = sfield.at(agent)
+    visits, hit = sfield.occupancy(agent)
+    pooled = hit.mean(dim=0)
+    block = {"field": sfield.metrics(),
+             "start": {"seeds": seeds, "success": success.cpu().tolist(), "ret": ret.cpu().tolist(),
+                       "steps": steps.cpu().tolist()},
+             # P(the episode of a seed drawn uniformly terminates at action t), t = 1..max_steps, and P(it is truncated)
+             "length_distribution": {"terminated_at": pooled.cpu().tolist(), "truncated": float(1.0 - pooled.sum())}}
+    return block, visits
+
+
+def draw_maps(field, agent, name: str, k: int, out_dir: str, sampled=None) -> int:
+    """<out_dir>/<name>_map<i>.png for the first k maps; 0 when matplotlib is missing.  sampled = (SampledField,
+    visits): two more panels."""
     try:
         import matplotlib
 
@@ -70,13 +97,23 @@ def draw_maps(field, agent, name: str, k: int, out_dir: str) -> int:
     trapped = torch.where(free[:, 0], ((steps == -1) & free).sum(dim=1).float(), nan[:, 0]).cpu()
     value = torch.where(free, field.value[:k], torch.full_like(steps, float("-inf"))).amax(dim=1)
     value = torch.where(torch.isinf(value), nan[:, 0], value).cpu()
+    extra = []
+    if sampled is not None:
+        sfield, visits = sampled
+        best = torch.nan_to_num(sfield.success[:k], nan=float("-inf")).amax(dim=1)
+        best = torch.where(torch.isinf(best), nan[:, 0].to(best.dtype), best).cpu()
+        seen = torch.where(free[:, 0], visits[:k].sum(dim=1), nan[:, 0].to(visits.dtype)).cpu()
+        extra = [(best, "sampled: P(success) (greatest over directions)", "viridis"),
+                 (seen, "sampled: expected visits (summed over directions)", "cividis")]
     for i in range(k):
-        fig, ax = plt.subplots(1, 4, figsize=(18, 4.8))
+        fig, ax = plt.subplots(1, 4 + len(extra), figsize=(18 + 4.5 * len(extra), 4.8))
         ax[0].imshow(frames[i].numpy())
         ax[0].set_title(f"{name} map {i}")
-        for a, img, title, cmap in ((ax[1], least[i], "steps to the goal (least over directions)", "viridis_r"),
-                                    (ax[2], trapped[i], "trapped directions", "Reds"),
-                                    (ax[3], value[i], "value (greatest over directions)", "magma")):
+        panels = [(ax[1], least[i], "steps to the goal (least over directions)", "viridis_r"),
+                  (ax[2], trapped[i], "trapped directions", "Reds"),
+                  (ax[3], value[i], "value (greatest over directions)", "magma")]
+        panels += [(ax[4 + j], img[i], title, cmap) for j, (img, title, cmap) in enumerate(extra)]
+        for a, img, title, cmap in panels:
             im = a.imshow(img.numpy(), cmap=cmap, vmin=0 if a is ax[2] else None, vmax=4 if a is ax[2] else None)
             a.set_title(title)
             fig.colorbar(im, ax=a, fraction=0.046)
@@ -118,8 +155,17 @@ def main(argv=None):
         print(f"    {d:<11} solved {m['solved_rate']:.3f} | trapped {m['trapped_rate']:.3f} | timeout "
               f"{m['timeout_rate']:.3f} | spl {m['spl']:.3f} | optimal actions {m['optimal_action_rate']:.3f} | "
               f"value rmse {m['value_rmse']:.3f} | {m['n_solvable']}/{m['n_free']} poses solvable")
+        drawn = None
+        if args.sampled:
+            sfield = sampled_field(policy, field.walls, field.goal, size, ms, gamma=args.gamma)
+            per[d]["sampled"], visits = sampled_block(sfield, agent, seeds)
+            sm = per[d]["sampled"]["field"]
+            print(f"    {'':<11} sampled: success {sm['success_rate']:.3f} | return {sm['expected_return']:.3f} | steps "
+                  f"{sm['expected_steps']:.1f} | regret {sm['return_regret']:.3f} | value rmse "
+                  f"{sm['value_rmse_sampled']:.3f}")
+            drawn = (sfield, visits)
         if not args.no_plots:
-            n = draw_maps(field, agent, d, args.maps_to_draw, args.out_dir)
+            n = draw_maps(field, agent, d, args.maps_to_draw, args.out_dir, sampled=drawn)
             if n == 0 and args.maps_to_draw > 0:
                 print("[*] matplotlib is not installed: maps not drawn")
     out = {"model_path": args.model_path, "difficulties": args.difficulties, "num_tasks": args.num_tasks,

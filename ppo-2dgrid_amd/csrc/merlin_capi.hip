@@ -444,6 +444,58 @@ int merlin_policy_paths_host(const uint32_t *walls, const int32_t *goal, const i
     return MERLIN_OK;
 }
 
+// the argument rules the four sampled-policy entries share; 0: go on, -1: nothing to do
+static int chain_args(int64_t n_maps, int32_t size, int32_t horizon, bool required, bool any_output) {
+    if (size < 5 || size > 32) return fail(MERLIN_E_INVALID, "grid size must be in [5, 32]");
+    if (horizon < 1 || horizon > 16384) return fail(MERLIN_E_INVALID, "horizon must be in [1, 16384]");
+    if (n_maps < 0) return fail(MERLIN_E_INVALID, "negative map count");
+    if (n_maps == 0) return -1;
+    if (!required) return fail(MERLIN_E_INVALID, "null argument");
+    if (!any_output) return fail(MERLIN_E_INVALID, "no output requested");
+    return 0;
+}
+
+int merlin_policy_chain(const uint32_t *walls, const int32_t *goal, const float *probs, int64_t n_maps, int32_t size,
+                        int32_t horizon, double gamma, double *success, double *ret, double *steps, double *disc,
+                        void *stream) {
+    const int rc = chain_args(n_maps, size, horizon, walls && goal && probs, success || ret || steps || disc);
+    if (rc) return rc < 0 ? MERLIN_OK : rc;
+    HIP_TRY(merlin::launch_policy_chain(walls, goal, probs, n_maps, size, horizon, gamma, success, ret, steps, disc,
+                                        (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_policy_chain_host(const uint32_t *walls, const int32_t *goal, const float *probs, int64_t n_maps,
+                             int32_t size, int32_t horizon, double gamma, double *success, double *ret,
+                             double *steps, double *disc) {
+    const int rc = chain_args(n_maps, size, horizon, walls && goal && probs, success || ret || steps || disc);
+    if (rc) return rc < 0 ? MERLIN_OK : rc;
+    merlin::policy_chain_host(walls, goal, probs, n_maps, size, horizon, gamma, success, ret, steps, disc);
+    return MERLIN_OK;
+}
+
+int merlin_policy_occupancy(const uint32_t *walls, const int32_t *goal, const float *probs, const int32_t *agent,
+                            int64_t n_maps, int32_t size, int32_t horizon, double *visits, double *hit,
+                            void *stream) {
+    int rc = chain_args(n_maps, size, horizon, walls && goal && probs && agent, visits || hit);
+    if (rc) return rc < 0 ? MERLIN_OK : rc;
+    DeviceWs *ws = nullptr;
+    rc = device_ws(&ws);
+    if (rc) return rc;
+    HIP_TRY(merlin::launch_policy_occupancy(walls, goal, probs, agent, n_maps, size, horizon, visits, hit,
+                                            ws->tower_err, (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_policy_occupancy_host(const uint32_t *walls, const int32_t *goal, const float *probs,
+                                 const int32_t *agent, int64_t n_maps, int32_t size, int32_t horizon,
+                                 double *visits, double *hit) {
+    const int rc = chain_args(n_maps, size, horizon, walls && goal && probs && agent, visits || hit);
+    if (rc) return rc < 0 ? MERLIN_OK : rc;
+    merlin::policy_occupancy_host(walls, goal, probs, agent, n_maps, size, horizon, visits, hit);
+    return MERLIN_OK;
+}
+
 int64_t merlin_env_config_layout(int64_t *offsets_host, int32_t n_fields) {
     const int64_t off[MERLIN_ENV_CONFIG_FIELDS] = {
         (int64_t)offsetof(merlin_env_config, num_envs),     (int64_t)offsetof(merlin_env_config, size),

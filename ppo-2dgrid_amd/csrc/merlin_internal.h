@@ -338,6 +338,19 @@ hipError_t launch_policy_paths(const uint32_t *walls, const int32_t *goal, const
                                int size, int16_t *steps, hipStream_t s);
 void policy_paths_host(const uint32_t *walls, const int32_t *goal, const int8_t *action, int64_t n_maps, int S,
                        int16_t *steps);
+// the sampled-policy field (merlin_chain.hip): probs float[n_maps][4][size][size][3]; the backward pass' four
+// double[n_maps][4][size][size] outputs and the forward pass' visits (same shape) and hit double[n_maps][horizon],
+// each nullable
+hipError_t launch_policy_chain(const uint32_t *walls, const int32_t *goal, const float *probs, int64_t n_maps, int size,
+                               int horizon, double gamma, double *success, double *ret, double *steps, double *disc,
+                               hipStream_t s);
+hipError_t launch_policy_occupancy(const uint32_t *walls, const int32_t *goal, const float *probs,
+                                   const int32_t *agent, int64_t n_maps, int size, int horizon, double *visits,
+                                   double *hit, uint32_t *err, hipStream_t s);
+void policy_chain_host(const uint32_t *walls, const int32_t *goal, const float *probs, int64_t n_maps, int S, int T,
+                       double gamma, double *success, double *ret, double *steps, double *disc);
+void policy_occupancy_host(const uint32_t *walls, const int32_t *goal, const float *probs, const int32_t *agent,
+                           int64_t n_maps, int S, int T, double *visits, double *hit);
 hipError_t launch_obs_expand_f32(const uint32_t *codes, const int64_t *index, int64_t n, float *out,
                                  float scale, int layout, hipStream_t s);
 hipError_t launch_obs_expand_u8(const uint32_t *codes, const int64_t *index, int64_t n, uint8_t *out,

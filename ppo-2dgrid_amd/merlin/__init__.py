@@ -12,9 +12,11 @@ from .few_shot import FewShotAdapter
 from .ppo import PPO
 from .recording import Recording, record_episodes
 from .rollout_buffer import CodeRolloutBuffer, RolloutBuffer
+from .sampled_field import SampledField, sampled_field, sampled_field_for_seeds, sampled_field_from_probs
 from .scenario_creator import ScenarioCreator
 from .utils.utils import get_device, set_seed
 from .utils.utils_rl import compute_gae_standard, layer_init
 
 __all__ = ["CNNActorCritic", "MLPActorCritic", "MerlinEnv", "MerlinVecEnv", "FewShotAdapter", "PPO", "CodeRolloutBuffer",
-           "Recording", "record_episodes", "RolloutBuffer", "ScenarioCreator", "get_device", "set_seed", "compute_gae_standard", "layer_init"]
+           "Recording", "record_episodes", "RolloutBuffer", "SampledField", "sampled_field", "sampled_field_for_seeds",
+           "sampled_field_from_probs", "ScenarioCreator", "get_device", "set_seed", "compute_gae_standard", "layer_init"]

@@ -202,6 +202,10 @@ def lib():
     L.merlin_view_codes.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp]
     L.merlin_policy_paths.argtypes = [vp, vp, vp, i64, i32, vp, vp]
     L.merlin_policy_paths_host.argtypes = [vp, vp, vp, i64, i32, vp]
+    L.merlin_policy_chain.argtypes = [vp, vp, vp, i64, i32, i32, C.c_double, vp, vp, vp, vp, vp]
+    L.merlin_policy_chain_host.argtypes = [vp, vp, vp, i64, i32, i32, C.c_double, vp, vp, vp, vp]
+    L.merlin_policy_occupancy.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp]
+    L.merlin_policy_occupancy_host.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp]
     check_env_config_layout(L)
     _lib = L
     return L
@@ -258,6 +262,7 @@ EXPORTED_SYMBOLS = (
     "merlin_shortest_paths", "merlin_env_optimal_steps", "merlin_shortest_paths_host",
     "merlin_h3_walk_blocks",
     "merlin_view_codes", "merlin_policy_paths", "merlin_policy_paths_host",
+    "merlin_policy_chain", "merlin_policy_chain_host", "merlin_policy_occupancy", "merlin_policy_occupancy_host",
 )
 
 
@@ -635,6 +640,181 @@ def policy_paths_host(walls, goal, action, size: int):
                                              action.ctypes.data_as(vp), M, S, steps.ctypes.data_as(vp)),
               "merlin_policy_paths_host")
     return steps
+
+
+CHAIN_OUTPUTS = ("success", "ret", "steps", "disc")
+OCCUPANCY_OUTPUTS = ("visits", "hit")
+MAX_HORIZON = 16384  # merlin_policy_chain / merlin_policy_occupancy: horizon in 1..16384
+
+
+def policy_chain_bytes(n_maps: int, size: int, n_outputs: int = 4) -> int:
+    """Algorithmic bytes of k_policy_chain: the rows, goal and probabilities read, the requested fields written."""
+    return n_maps * (size * 4 + 8 + 4 * size * size * (12 + 8 * n_outputs))
+
+
+def policy_occupancy_bytes(n_maps: int, size: int, horizon: int, visits: bool = True, hit: bool = True) -> int:
+    """Algorithmic bytes of k_policy_occupancy: the rows, goal, pose and probabilities read, visits and hit written."""
+    return n_maps * (size * 4 + 8 + 16 + 4 * size * size * (12 + 8 * int(visits)) + 8 * horizon * int(hit))
+
+
+def _check_probs(name: str, walls, probs, size: int, xp) -> None:
+    """One reduction over the free poses' rows: every entry >= 0 and a finite sum above 0 (the kernels do not check)."""
+    x = xp.arange(size, device=walls.device) if xp is torch else xp.arange(size)
+    free = ((walls.long() if xp is torch else walls.astype("int64"))[:, None, :, None] >> x) & 1
+    s = probs.sum(-1)
+    good = (probs >= 0).all(-1) & xp.isfinite(s) & (s > 0)
+    if bool(((free == 0) & ~good).any()):
+        raise MerlinNativeError(f"{name}: a free pose's probabilities have a negative or non-finite entry or sum to "
+                                "zero")
+
+
+def _f64_outputs(name, names, wanted, out, shapes, make):
+    """The output tensors / arrays in `names` order, None where not wanted; `out`: a dict of caller's buffers."""
+    wanted = tuple(wanted)
+    if not wanted or any(w not in names for w in wanted):
+        raise MerlinNativeError(f"{name}: outputs must be a non-empty subset of {names}, got {wanted}")
+    res = []
+    for k in names:
+        if k not in wanted:
+            res.append(None)
+            continue
+        buf = (out or {}).get(k)
+        res.append(make(k, buf, shapes[k]))
+    return res
+
+
+def _torch_f64(name, device):
+    def make(k, buf, shape):
+        n = 1
+        for v in shape:
+            n *= v
+        if buf is None:
+            return torch.empty(shape, dtype=torch.float64, device=device)
+        if buf.dtype != torch.float64 or not buf.is_contiguous() or buf.numel() != n or buf.device != device:
+            raise MerlinNativeError(f"{name}: out[{k!r}] must be a contiguous float64 tensor of {n} elements")
+        return buf.view(shape)
+    return make
+
+
+def policy_chain(walls: torch.Tensor, goal: torch.Tensor, probs: torch.Tensor, size: int, horizon: int,
+                 gamma: float = 0.99, outputs=CHAIN_OUTPUTS, out: dict | None = None, validate: bool = True):
+    """(success, ret, steps, disc), each float64[M, 4, size, size] indexed [dir][y][x] or None where not in `outputs`:
+    of an episode started in each pose under the sampled policy probs float32[M, 4, size, size, 3] (action 0 left, 1
+    right, 2 forward), the probability of reaching the goal within `horizon` actions, the expected reward, the
+    expected length and the discounted return from step 0; NaN at wall poses (merlin_policy_chain;
+    include/merlin_hip.h has the definitions).  walls int32[M, size], goal int32[M, 2], as MerlinVecEnv.snapshot()
+    gives them.  `out`: a dict of contiguous float64 tensors to write into.  validate=True reads one reduction back (a
+    host sync: pass False inside a graph capture) and raises if a free pose's row is negative, non-finite or zero."""
+    S, T = int(size), int(horizon)
+    M = int(walls.shape[0])
+    assert walls.dtype == torch.int32 and walls.shape == (M, S) and walls.is_contiguous()
+    assert goal.dtype == torch.int32 and goal.shape == (M, 2) and goal.is_contiguous()
+    assert probs.dtype == torch.float32 and probs.shape == (M, 4, S, S, 3) and probs.is_contiguous()
+    if validate and M:
+        _check_probs("policy_chain", walls, probs, S, torch)
+    res = _f64_outputs("policy_chain", CHAIN_OUTPUTS, outputs, out, dict.fromkeys(CHAIN_OUTPUTS, (M, 4, S, S)),
+                       _torch_f64("policy_chain", walls.device))
+    n_out = sum(r is not None for r in res)
+    with torch.cuda.device(walls.device), KernelTimer.span("k_policy_chain", policy_chain_bytes(M, S, n_out)):
+        rc = lib().merlin_policy_chain(ptr(walls), ptr(goal), ptr(probs), M, S, T, float(gamma),
+                                             *(ptr(r) for r in res), stream_of(walls))
+        check(rc, "merlin_policy_chain")
+    return tuple(res)
+
+
+def policy_occupancy(walls: torch.Tensor, goal: torch.Tensor, probs: torch.Tensor, agent: torch.Tensor, size: int,
+                     horizon: int, outputs=OCCUPANCY_OUTPUTS, out: dict | None = None, validate: bool = True):
+    """(visits float64[M, 4, size, size], hit float64[M, horizon]), None where not in `outputs`: of an episode started
+    in pose agent[m] = (x, y, dir, 0) of map m under the sampled policy `probs`, the expected number of visits to
+    every pose (0 at wall poses) and the probability hit[m, t - 1] that it terminates at action t
+    (merlin_policy_occupancy).  An invalid start pose gives NaN rows and raises DEVERR_BAD_FRAME (tower_errors).
+    Arguments as policy_chain."""
+    S, T = int(size), int(horizon)
+    M = int(walls.shape[0])
+    assert walls.dtype == torch.int32 and walls.shape == (M, S) and walls.is_contiguous()
+    assert goal.dtype == torch.int32 and goal.shape == (M, 2) and goal.is_contiguous()
+    assert probs.dtype == torch.float32 and probs.shape == (M, 4, S, S, 3) and probs.is_contiguous()
+    assert agent.dtype == torch.int32 and agent.shape == (M, 4) and agent.is_contiguous()
+    if validate and M:
+        _check_probs("policy_occupancy", walls, probs, S, torch)
+    res = _f64_outputs("policy_occupancy", OCCUPANCY_OUTPUTS, outputs, out,
+                       {"visits": (M, 4, S, S), "hit": (M, max(T, 0))}, _torch_f64("policy_occupancy", walls.device))
+    nbytes = policy_occupancy_bytes(M, S, T, res[0] is not None, res[1] is not None)
+    with torch.cuda.device(walls.device), KernelTimer.span("k_policy_occupancy", nbytes):
+        rc = lib().merlin_policy_occupancy(ptr(walls), ptr(goal), ptr(probs), ptr(agent), M, S, T,
+                                                 ptr(res[0]), ptr(res[1]), stream_of(walls))
+        check(rc, "merlin_policy_occupancy")
+    return tuple(res)
+
+
+def _chain_host_args(walls, goal, probs, size):
+    import numpy as np
+
+    S = int(size)
+    walls = np.ascontiguousarray(np.asarray(walls).astype(np.uint32, copy=False))
+    M = int(walls.shape[0])
+    goal = np.ascontiguousarray(goal, dtype=np.int32)
+    probs = np.ascontiguousarray(probs, dtype=np.float32)
+    assert walls.shape == (M, S) and goal.shape == (M, 2) and probs.shape == (M, 4, S, S, 3)
+    return S, M, walls, goal, probs
+
+
+def _numpy_f64(name):
+    import numpy as np
+
+    def make(k, buf, shape):
+        if buf is None:
+            return np.empty(shape, dtype=np.float64)
+        if buf.dtype != np.float64 or not buf.flags.c_contiguous or buf.shape != tuple(shape):
+            raise MerlinNativeError(f"{name}: out[{k!r}] must be a C-contiguous float64 array of shape {shape}")
+        return buf
+    return make
+
+
+def policy_chain_host(walls, goal, probs, size: int, horizon: int, gamma: float = 0.99, outputs=CHAIN_OUTPUTS,
+                      out: dict | None = None, validate: bool = True):
+    """policy_chain on numpy arrays, on the CPU by the library's successor-table recursion (merlin_policy_chain_host):
+    walls uint32 / int32 [M, size], goal int32[M, 2], probs float32[M, 4, size, size, 3]."""
+    import numpy as np
+
+    S, M, walls, goal, probs = _chain_host_args(walls, goal, probs, size)
+    if validate and M:
+        _check_probs("policy_chain_host", walls, probs, S, np)
+    res = _f64_outputs("policy_chain_host", CHAIN_OUTPUTS, outputs, out,
+                       dict.fromkeys(CHAIN_OUTPUTS, (M, 4, max(S, 0), max(S, 0))), _numpy_f64("policy_chain_host"))
+    vp = C.c_void_p
+    n_out = sum(r is not None for r in res)
+    with KernelTimer.span("policy_chain_host", policy_chain_bytes(M, S, n_out)):
+        rc = lib().merlin_policy_chain_host(walls.ctypes.data_as(vp), goal.ctypes.data_as(vp),
+                                            probs.ctypes.data_as(vp), M, S, int(horizon), float(gamma),
+                                            *(None if r is None else r.ctypes.data_as(vp) for r in res))
+        check(rc, "merlin_policy_chain_host")
+    return tuple(res)
+
+
+def policy_occupancy_host(walls, goal, probs, agent, size: int, horizon: int, outputs=OCCUPANCY_OUTPUTS,
+                          out: dict | None = None, validate: bool = True):
+    """policy_occupancy on numpy arrays, on the CPU by the library's scatter over the successor table
+    (merlin_policy_occupancy_host); agent int32[M, 4].  An invalid start pose gives NaN rows (no error flag)."""
+    import numpy as np
+
+    S, M, walls, goal, probs = _chain_host_args(walls, goal, probs, size)
+    agent = np.ascontiguousarray(agent, dtype=np.int32)
+    assert agent.shape == (M, 4)
+    T = int(horizon)
+    if validate and M:
+        _check_probs("policy_occupancy_host", walls, probs, S, np)
+    res = _f64_outputs("policy_occupancy_host", OCCUPANCY_OUTPUTS, outputs, out,
+                       {"visits": (M, 4, max(S, 0), max(S, 0)), "hit": (M, max(T, 0))},
+                       _numpy_f64("policy_occupancy_host"))
+    vp = C.c_void_p
+    nbytes = policy_occupancy_bytes(M, S, T, res[0] is not None, res[1] is not None)
+    with KernelTimer.span("policy_occupancy_host", nbytes):
+        rc = lib().merlin_policy_occupancy_host(walls.ctypes.data_as(vp), goal.ctypes.data_as(vp),
+                                                probs.ctypes.data_as(vp), agent.ctypes.data_as(vp), M, S, T,
+                                                *(None if r is None else r.ctypes.data_as(vp) for r in res))
+        check(rc, "merlin_policy_occupancy_host")
+    return tuple(res)
 
 
 # ---------------------------------------------------------------------------

@@ -668,6 +668,15 @@ class CNNActorCritic(nn.Module):
         action = _sample_or_argmax(logits, logp_all, probs, deterministic)
         return action, logp_all.gather(-1, action.unsqueeze(-1)).squeeze(-1), value
 
+    def probs_codes(self, codes, index=None):
+        """(probs float32[n, 3], value [n]): the probabilities act_codes samples from -- the softmax of the same
+        logits -- for the sampled-policy field (merlin/sampled_field.py), whose chain has three actions."""
+        if self.actor[2].out_features != 3:
+            raise ValueError(f"probs_codes: the sampled-policy field has 3 actions, this policy has "
+                             f"{self.actor[2].out_features}")
+        logits, value = self._forward_codes(codes, index)
+        return _categorical(logits)[1].float(), value
+
     def evaluate_codes(self, codes, actions, index=None, groups=None):
         """groups = (rep_idx, inv) (merlin.dedup.FrameGroups.minibatch): the towers run on the
         distinct frames rep_idx only and sample k takes row inv[k] (same values and gradients)."""
