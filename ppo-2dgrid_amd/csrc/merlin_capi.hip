@@ -49,6 +49,23 @@ int hip_fail(hipError_t e, const char *what) {
         if (_e != hipSuccess) return hip_fail(_e, #expr); \
     } while (0)
 
+// The map entries' shared argument rules, in order: the grid size, the entry's own range check (`range_err`: its
+// message, or null), the count's sign, the needed pointers.  0: go on, -1: a zero count, nothing to do, else the code.
+int map_args(int32_t size, const char *range_err, int64_t n, const char *negative, bool required) {
+    if (size < 5 || size > 32) return fail(MERLIN_E_INVALID, "grid size must be in [5, 32]");
+    if (range_err) return fail(MERLIN_E_INVALID, range_err);
+    if (n < 0) return fail(MERLIN_E_INVALID, negative);
+    if (n == 0) return -1;
+    if (!required) return fail(MERLIN_E_INVALID, "null argument");
+    return 0;
+}
+
+#define ARGS_TRY(expr)                                      \
+    do {                                                    \
+        const int _rc = (expr);                             \
+        if (_rc) return _rc < 0 ? MERLIN_OK : _rc;          \
+    } while (0)
+
 // ---------------------------------------------------------------------------
 // numpy SeedSequence(seed).generate_state(4, uint64) -> PCG64 seeding
 // (numpy/random/bit_generator.pyx mix_entropy / generate_state,
@@ -345,11 +362,9 @@ int merlin_frame_atlas(int32_t tile_size, uint8_t *out_host) {
 int merlin_render_frames(const uint32_t *walls, const int32_t *goal, const int32_t *agent, const int32_t *map_index,
                          int64_t n_frames, int32_t size, int32_t tile_size, int32_t highlight, uint8_t *out,
                          void *stream) {
-    if (size < 5 || size > 32) return fail(MERLIN_E_INVALID, "grid size must be in [5, 32]");
-    if (tile_size < FRAME_TS_MIN || tile_size > FRAME_TS_MAX) return fail(MERLIN_E_INVALID, "tile_size must be in [4, 32]");
-    if (n_frames < 0) return fail(MERLIN_E_INVALID, "negative frame count");
-    if (n_frames == 0) return MERLIN_OK;
-    if (!walls || !agent || !out) return fail(MERLIN_E_INVALID, "null argument");
+    const bool ts_ok = tile_size >= FRAME_TS_MIN && tile_size <= FRAME_TS_MAX;
+    const char *ts_err = ts_ok ? nullptr : "tile_size must be in [4, 32]";
+    ARGS_TRY(map_args(size, ts_err, n_frames, "negative frame count", walls && agent && out));
     const uint8_t *atlas = nullptr;
     uint32_t *err = nullptr;
     int rc = device_frame_atlas(tile_size, &atlas, &err);
@@ -384,10 +399,7 @@ int merlin_env_snapshot(merlin_env *e, uint32_t *walls, int32_t *goal, int32_t *
 
 int merlin_shortest_paths(const uint32_t *walls, const int32_t *goal, const int32_t *agent, const int32_t *map_index,
                           int64_t n, int32_t size, int32_t *dist, int16_t *field, void *stream) {
-    if (size < 5 || size > 32) return fail(MERLIN_E_INVALID, "grid size must be in [5, 32]");
-    if (n < 0) return fail(MERLIN_E_INVALID, "negative query count");
-    if (n == 0) return MERLIN_OK;
-    if (!walls || !goal || !agent || !dist) return fail(MERLIN_E_INVALID, "null argument");
+    ARGS_TRY(map_args(size, nullptr, n, "negative query count", walls && goal && agent && dist));
     HIP_TRY(merlin::launch_shortest_paths(walls, goal, agent, map_index, n, size, dist, field, (hipStream_t)stream));
     return MERLIN_OK;
 }
@@ -402,20 +414,14 @@ int merlin_env_optimal_steps(merlin_env *e, int32_t *dist, int16_t *field, void 
 
 int merlin_shortest_paths_host(const uint32_t *walls, const int32_t *goal, const int32_t *agent, int64_t n,
                                int32_t size, int32_t *dist, int16_t *field) {
-    if (size < 5 || size > 32) return fail(MERLIN_E_INVALID, "grid size must be in [5, 32]");
-    if (n < 0) return fail(MERLIN_E_INVALID, "negative query count");
-    if (n == 0) return MERLIN_OK;
-    if (!walls || !goal || !agent || !dist) return fail(MERLIN_E_INVALID, "null argument");
+    ARGS_TRY(map_args(size, nullptr, n, "negative query count", walls && goal && agent && dist));
     merlin::shortest_paths_host(walls, goal, agent, n, size, dist, field);
     return MERLIN_OK;
 }
 
 int merlin_view_codes(const uint32_t *walls, const int32_t *goal, const int32_t *agent, const int32_t *map_index,
                       int64_t n, int32_t size, uint32_t *codes, void *stream) {
-    if (size < 5 || size > 32) return fail(MERLIN_E_INVALID, "grid size must be in [5, 32]");
-    if (n < 0) return fail(MERLIN_E_INVALID, "negative query count");
-    if (n == 0) return MERLIN_OK;
-    if (!walls || !agent || !codes) return fail(MERLIN_E_INVALID, "null argument");
+    ARGS_TRY(map_args(size, nullptr, n, "negative query count", walls && agent && codes));
     DeviceWs *ws = nullptr;
     int rc = device_ws(&ws);
     if (rc) return rc;
@@ -426,40 +432,29 @@ int merlin_view_codes(const uint32_t *walls, const int32_t *goal, const int32_t 
 
 int merlin_policy_paths(const uint32_t *walls, const int32_t *goal, const int8_t *action, int64_t n_maps,
                         int32_t size, int16_t *steps, void *stream) {
-    if (size < 5 || size > 32) return fail(MERLIN_E_INVALID, "grid size must be in [5, 32]");
-    if (n_maps < 0) return fail(MERLIN_E_INVALID, "negative map count");
-    if (n_maps == 0) return MERLIN_OK;
-    if (!walls || !goal || !action || !steps) return fail(MERLIN_E_INVALID, "null argument");
+    ARGS_TRY(map_args(size, nullptr, n_maps, "negative map count", walls && goal && action && steps));
     HIP_TRY(merlin::launch_policy_paths(walls, goal, action, n_maps, size, steps, (hipStream_t)stream));
     return MERLIN_OK;
 }
 
 int merlin_policy_paths_host(const uint32_t *walls, const int32_t *goal, const int8_t *action, int64_t n_maps,
                              int32_t size, int16_t *steps) {
-    if (size < 5 || size > 32) return fail(MERLIN_E_INVALID, "grid size must be in [5, 32]");
-    if (n_maps < 0) return fail(MERLIN_E_INVALID, "negative map count");
-    if (n_maps == 0) return MERLIN_OK;
-    if (!walls || !goal || !action || !steps) return fail(MERLIN_E_INVALID, "null argument");
+    ARGS_TRY(map_args(size, nullptr, n_maps, "negative map count", walls && goal && action && steps));
     merlin::policy_paths_host(walls, goal, action, n_maps, size, steps);
     return MERLIN_OK;
 }
 
-// the argument rules the four sampled-policy entries share; 0: go on, -1: nothing to do
+// map_args for the four sampled-policy entries: the horizon's range, and at least one output
 static int chain_args(int64_t n_maps, int32_t size, int32_t horizon, bool required, bool any_output) {
-    if (size < 5 || size > 32) return fail(MERLIN_E_INVALID, "grid size must be in [5, 32]");
-    if (horizon < 1 || horizon > 16384) return fail(MERLIN_E_INVALID, "horizon must be in [1, 16384]");
-    if (n_maps < 0) return fail(MERLIN_E_INVALID, "negative map count");
-    if (n_maps == 0) return -1;
-    if (!required) return fail(MERLIN_E_INVALID, "null argument");
-    if (!any_output) return fail(MERLIN_E_INVALID, "no output requested");
-    return 0;
+    const char *t_err = horizon >= 1 && horizon <= 16384 ? nullptr : "horizon must be in [1, 16384]";
+    const int rc = map_args(size, t_err, n_maps, "negative map count", required);
+    return rc || any_output ? rc : fail(MERLIN_E_INVALID, "no output requested");
 }
 
 int merlin_policy_chain(const uint32_t *walls, const int32_t *goal, const float *probs, int64_t n_maps, int32_t size,
                         int32_t horizon, double gamma, double *success, double *ret, double *steps, double *disc,
                         void *stream) {
-    const int rc = chain_args(n_maps, size, horizon, walls && goal && probs, success || ret || steps || disc);
-    if (rc) return rc < 0 ? MERLIN_OK : rc;
+    ARGS_TRY(chain_args(n_maps, size, horizon, walls && goal && probs, success || ret || steps || disc));
     HIP_TRY(merlin::launch_policy_chain(walls, goal, probs, n_maps, size, horizon, gamma, success, ret, steps, disc,
                                         (hipStream_t)stream));
     return MERLIN_OK;
@@ -468,8 +463,7 @@ int merlin_policy_chain(const uint32_t *walls, const int32_t *goal, const float 
 int merlin_policy_chain_host(const uint32_t *walls, const int32_t *goal, const float *probs, int64_t n_maps,
                              int32_t size, int32_t horizon, double gamma, double *success, double *ret,
                              double *steps, double *disc) {
-    const int rc = chain_args(n_maps, size, horizon, walls && goal && probs, success || ret || steps || disc);
-    if (rc) return rc < 0 ? MERLIN_OK : rc;
+    ARGS_TRY(chain_args(n_maps, size, horizon, walls && goal && probs, success || ret || steps || disc));
     merlin::policy_chain_host(walls, goal, probs, n_maps, size, horizon, gamma, success, ret, steps, disc);
     return MERLIN_OK;
 }
@@ -477,10 +471,9 @@ int merlin_policy_chain_host(const uint32_t *walls, const int32_t *goal, const f
 int merlin_policy_occupancy(const uint32_t *walls, const int32_t *goal, const float *probs, const int32_t *agent,
                             int64_t n_maps, int32_t size, int32_t horizon, double *visits, double *hit,
                             void *stream) {
-    int rc = chain_args(n_maps, size, horizon, walls && goal && probs && agent, visits || hit);
-    if (rc) return rc < 0 ? MERLIN_OK : rc;
+    ARGS_TRY(chain_args(n_maps, size, horizon, walls && goal && probs && agent, visits || hit));
     DeviceWs *ws = nullptr;
-    rc = device_ws(&ws);
+    const int rc = device_ws(&ws);
     if (rc) return rc;
     HIP_TRY(merlin::launch_policy_occupancy(walls, goal, probs, agent, n_maps, size, horizon, visits, hit,
                                             ws->tower_err, (hipStream_t)stream));
@@ -490,8 +483,7 @@ int merlin_policy_occupancy(const uint32_t *walls, const int32_t *goal, const fl
 int merlin_policy_occupancy_host(const uint32_t *walls, const int32_t *goal, const float *probs,
                                  const int32_t *agent, int64_t n_maps, int32_t size, int32_t horizon,
                                  double *visits, double *hit) {
-    const int rc = chain_args(n_maps, size, horizon, walls && goal && probs && agent, visits || hit);
-    if (rc) return rc < 0 ? MERLIN_OK : rc;
+    ARGS_TRY(chain_args(n_maps, size, horizon, walls && goal && probs && agent, visits || hit));
     merlin::policy_occupancy_host(walls, goal, probs, agent, n_maps, size, horizon, visits, hit);
     return MERLIN_OK;
 }

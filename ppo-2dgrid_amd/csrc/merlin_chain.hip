@@ -20,14 +20,19 @@
 // 512 and 1,024 threads that holds S^2 cells (S <= 16, S <= 22, S <= 32): 16, 32 or 64 KiB of LDS.
 // Float64 throughout; the file is compiled with -ffp-contract=off like the rest, so the host restatements below, which
 // keep the kernels' order of operations inside a term, differ from them by the order of a pose's incoming terms only.
+// Grid geometry (direction vectors, free_at, the goal; the host's map view and pose numbering) is merlin_grid.h's.
 #include "merlin_internal.h"
+#include "merlin_grid.h"
 
 #include <algorithm>
 #include <limits>
+#include <type_traits>
 #include <vector>
 
 namespace merlin {
 namespace {
+
+using namespace grid;
 
 // What a thread knows of its cell: (x, y) and whether it is a free cell of the grid.
 struct Cell {
@@ -52,10 +57,6 @@ __device__ __forceinline__ void load_probs(const float *__restrict__ p, double &
     qF = p2 / s;
 }
 
-__device__ __forceinline__ bool free_at(const uint32_t *__restrict__ wrow, int S, int x, int y) {
-    return x >= 0 && x < S && y >= 0 && y < S && !((wrow[y] >> x) & 1u);
-}
-
 template <int BLK>
 __global__ __launch_bounds__(BLK) void k_policy_chain(const uint32_t *__restrict__ walls,
                                                        const int32_t *__restrict__ goal,
@@ -67,8 +68,7 @@ __global__ __launch_bounds__(BLK) void k_policy_chain(const uint32_t *__restrict
     const int c = threadIdx.x, cells = S * S;
     const uint32_t *wrow = walls + m * S;
     const Cell k = cell_of(wrow, S, c);
-    const int gx = goal[2 * m], gy = goal[2 * m + 1];
-    const bool goal_in = gx >= 0 && gx < S && gy >= 0 && gy < S;
+    const Goal gl = goal_of(goal, m, S);
 
     // qF is the forward probability as the recursion uses it: 0 where the front cell is the goal (that forward move
     // terminates: it is h_1, and g_t = 0 after it); src is the LDS slot the forward term reads, the front pose or,
@@ -81,8 +81,8 @@ __global__ __launch_bounds__(BLK) void k_policy_chain(const uint32_t *__restrict
         src[d] = d * BLK + c;
         if (k.live) {
             load_probs(probs + (((m * 4 + d) * S + k.y) * (int64_t)S + k.x) * 3, qL[d], qR[d], qF[d]);
-            const int fx = k.x + ((d == 0) - (d == 2)), fy = k.y + ((d == 1) - (d == 3));
-            if (goal_in && fx == gx && fy == gy) {
+            const int fx = k.x + dir_x(d), fy = k.y + dir_y(d);
+            if (gl.in && fx == gl.gx && fy == gl.gy) {
                 h[d] = qF[d];
                 qF[d] = 0.0;
             } else if (free_at(wrow, S, fx, fy)) {
@@ -162,9 +162,8 @@ __global__ __launch_bounds__(BLK) void k_policy_occupancy(const uint32_t *__rest
         return;
     }
     const Cell k = cell_of(wrow, S, c);
-    const int gx = goal[2 * m], gy = goal[2 * m + 1];
-    const bool goal_in = gx >= 0 && gx < S && gy >= 0 && gy < S;
-    const bool on_goal = goal_in && k.x == gx && k.y == gy && c < cells;
+    const Goal gl = goal_of(goal, m, S);
+    const bool on_goal = gl.in && k.x == gl.gx && k.y == gl.gy && c < cells;
 
     // back: the LDS slot of the pose whose forward move arrives here (-1: none -- the cell behind is a wall or off
     // the grid, or this cell is the goal, where a forward move ends the episode instead); qS: the forward
@@ -177,21 +176,21 @@ __global__ __launch_bounds__(BLK) void k_policy_occupancy(const uint32_t *__rest
         back[d] = -1;
         if (k.live) {
             load_probs(probs + (((m * 4 + d) * S + k.y) * (int64_t)S + k.x) * 3, qL[d], qR[d], qF[d]);
-            const int vx = (d == 0) - (d == 2), vy = (d == 1) - (d == 3);
+            const int vx = dir_x(d), vy = dir_y(d);
             const int fx = k.x + vx, fy = k.y + vy;
-            if (!(goal_in && fx == gx && fy == gy) && !free_at(wrow, S, fx, fy)) qS[d] = qF[d];
+            if (!(gl.in && fx == gl.gx && fy == gl.gy) && !free_at(wrow, S, fx, fy)) qS[d] = qF[d];
             if (!on_goal && free_at(wrow, S, k.x - vx, k.y - vy)) back[d] = d * BLK + (k.y - vy) * S + (k.x - vx);
             if (k.x == ax && k.y == ay && d == ad) mu[d] = 1.0;
         }
     }
     // hit[t] is written by one thread, the goal cell's (thread 0 for a goal outside the grid: nothing terminates): the
     // sum over the at most four free poses facing the goal, d = 0..3
-    const bool hitter = hit && (goal_in ? on_goal : c == 0);
+    const bool hitter = hit && (gl.in ? on_goal : c == 0);
     int face[4];
 #pragma unroll
     for (int d = 0; d < 4; d++) {
-        const int sx = gx - ((d == 0) - (d == 2)), sy = gy - ((d == 1) - (d == 3));
-        face[d] = (goal_in && free_at(wrow, S, sx, sy)) ? d * BLK + sy * S + sx : -1;
+        const int sx = gl.gx - dir_x(d), sy = gl.gy - dir_y(d);
+        face[d] = (gl.in && free_at(wrow, S, sx, sy)) ? d * BLK + sy * S + sx : -1;
     }
 
     for (int t = 0; t < T; t++) {
@@ -232,40 +231,40 @@ __global__ __launch_bounds__(BLK) void k_policy_occupancy(const uint32_t *__rest
     }
 }
 
+// launch(integral_constant BLK) with the smallest block of 256, 512 and 1,024 threads that holds size^2 cells
+template <class Launch>
+hipError_t with_block(int size, Launch launch) {
+    if (size * size <= 256)
+        launch(std::integral_constant<int, 256>{});
+    else if (size * size <= 512)
+        launch(std::integral_constant<int, 512>{});
+    else
+        launch(std::integral_constant<int, 1024>{});
+    return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_policy_chain(const uint32_t *walls, const int32_t *goal, const float *probs, int64_t n_maps, int size,
                                int horizon, double gamma, double *success, double *ret, double *steps, double *disc,
                                hipStream_t s) {
     if (n_maps <= 0) return hipSuccess;
-    const dim3 grid((unsigned)n_maps);
-    if (size * size <= 256)
-        hipLaunchKernelGGL(k_policy_chain<256>, grid, dim3(256), 0, s, walls, goal, probs, size, horizon, gamma,
-                           success, ret, steps, disc);
-    else if (size * size <= 512)
-        hipLaunchKernelGGL(k_policy_chain<512>, grid, dim3(512), 0, s, walls, goal, probs, size, horizon, gamma,
-                           success, ret, steps, disc);
-    else
-        hipLaunchKernelGGL(k_policy_chain<1024>, grid, dim3(1024), 0, s, walls, goal, probs, size, horizon, gamma,
-                           success, ret, steps, disc);
-    return hipGetLastError();
+    return with_block(size, [&](auto blk) {
+        constexpr int BLK = decltype(blk)::value;
+        hipLaunchKernelGGL(k_policy_chain<BLK>, dim3((unsigned)n_maps), dim3(BLK), 0, s, walls, goal, probs, size,
+                           horizon, gamma, success, ret, steps, disc);
+    });
 }
 
 hipError_t launch_policy_occupancy(const uint32_t *walls, const int32_t *goal, const float *probs,
                                    const int32_t *agent, int64_t n_maps, int size, int horizon, double *visits,
                                    double *hit, uint32_t *err, hipStream_t s) {
     if (n_maps <= 0) return hipSuccess;
-    const dim3 grid((unsigned)n_maps);
-    if (size * size <= 256)
-        hipLaunchKernelGGL(k_policy_occupancy<256>, grid, dim3(256), 0, s, walls, goal, probs, agent, size, horizon,
-                           visits, hit, err);
-    else if (size * size <= 512)
-        hipLaunchKernelGGL(k_policy_occupancy<512>, grid, dim3(512), 0, s, walls, goal, probs, agent, size, horizon,
-                           visits, hit, err);
-    else
-        hipLaunchKernelGGL(k_policy_occupancy<1024>, grid, dim3(1024), 0, s, walls, goal, probs, agent, size, horizon,
-                           visits, hit, err);
-    return hipGetLastError();
+    return with_block(size, [&](auto blk) {
+        constexpr int BLK = decltype(blk)::value;
+        hipLaunchKernelGGL(k_policy_occupancy<BLK>, dim3((unsigned)n_maps), dim3(BLK), 0, s, walls, goal, probs, agent,
+                           size, horizon, visits, hit, err);
+    });
 }
 
 // The host restatements go by another route: no cells and no neighbours, but one explicit successor table per map,
@@ -280,31 +279,31 @@ struct ChainTable {
     std::vector<uint8_t> live; // [P]
 };
 
-void build_table(const uint32_t *w, int gx, int gy, const float *probs, int S, ChainTable &tb) {
-    static const int DX[4] = {1, 0, -1, 0}, DY[4] = {0, 1, 0, -1};
+void build_table(const grid_host::MapView &mv, int gx, int gy, const float *probs, ChainTable &tb) {
+    const int S = mv.S;
     const int P = 4 * S * S;
     tb.P = P;
     tb.succ.assign((size_t)P * 3, 0);
     tb.q.assign((size_t)P * 3, 0.0);
     tb.live.assign(P, 0);
-    auto is_free = [&](int x, int y) { return x >= 0 && x < S && y >= 0 && y < S && !((w[y] >> x) & 1u); };
-    const bool goal_in = gx >= 0 && gx < S && gy >= 0 && gy < S;
+    const bool goal_in = mv.inside(gx, gy);
     for (int p = 0; p < P; p++) {
-        const int d = p / (S * S), y = (p / S) % S, x = p % S;
-        if (!is_free(x, y)) continue;
+        int d, y, x;
+        mv.decode(p, d, y, x);
+        if (!mv.is_free(x, y)) continue;
         tb.live[p] = 1;
         const double p0 = (double)probs[3 * p], p1 = (double)probs[3 * p + 1], p2 = (double)probs[3 * p + 2];
         const double s = (p0 + p1) + p2;
         tb.q[3 * p] = p0 / s;
         tb.q[3 * p + 1] = p1 / s;
         tb.q[3 * p + 2] = p2 / s;
-        tb.succ[3 * p] = (((d + 3) & 3) * S + y) * S + x;
-        tb.succ[3 * p + 1] = (((d + 1) & 3) * S + y) * S + x;
-        const int fx = x + DX[d], fy = y + DY[d];
+        tb.succ[3 * p] = mv.pose((d + 3) & 3, y, x);
+        tb.succ[3 * p + 1] = mv.pose((d + 1) & 3, y, x);
+        const int fx = x + grid_host::DX[d], fy = y + grid_host::DY[d];
         if (goal_in && fx == gx && fy == gy)
             tb.succ[3 * p + 2] = P;
-        else if (is_free(fx, fy))
-            tb.succ[3 * p + 2] = (d * S + fy) * S + fx;
+        else if (mv.is_free(fx, fy))
+            tb.succ[3 * p + 2] = mv.pose(d, fy, fx);
         else
             tb.succ[3 * p + 2] = p;
     }
@@ -321,7 +320,7 @@ void policy_chain_host(const uint32_t *walls, const int32_t *goal, const float *
     ChainTable tb;
     std::vector<double> u(P + 1), v(P + 1), a_s(P), a_r(P), a_n(P), a_d(P);
     for (int64_t m = 0; m < n_maps; m++) {
-        build_table(walls + m * S, goal[2 * m], goal[2 * m + 1], probs + m * (int64_t)P * 3, S, tb);
+        build_table({walls + m * S, S}, goal[2 * m], goal[2 * m + 1], probs + m * (int64_t)P * 3, tb);
         std::fill(u.begin(), u.end(), 0.0);
         u[P] = 1.0;
         std::fill(a_s.begin(), a_s.end(), 0.0);
@@ -368,18 +367,17 @@ void policy_occupancy_host(const uint32_t *walls, const int32_t *goal, const flo
     ChainTable tb;
     std::vector<double> mu(P + 1), nx(P + 1), vis(P);
     for (int64_t m = 0; m < n_maps; m++) {
-        const uint32_t *w = walls + m * S;
+        const grid_host::MapView mv{walls + m * S, S};
         const int ax = agent[4 * m], ay = agent[4 * m + 1], ad = agent[4 * m + 2];
-        const bool ok = ax >= 0 && ax < S && ay >= 0 && ay < S && ad >= 0 && ad <= 3 && !((w[ay] >> ax) & 1u);
-        if (!ok) {
+        if (!(mv.is_free(ax, ay) && ad >= 0 && ad <= 3)) {
             if (visits) std::fill(visits + m * (int64_t)P, visits + (m + 1) * (int64_t)P, nan);
             if (hit) std::fill(hit + m * (int64_t)T, hit + (m + 1) * (int64_t)T, nan);
             continue;
         }
-        build_table(w, goal[2 * m], goal[2 * m + 1], probs + m * (int64_t)P * 3, S, tb);
+        build_table(mv, goal[2 * m], goal[2 * m + 1], probs + m * (int64_t)P * 3, tb);
         std::fill(mu.begin(), mu.end(), 0.0);
         std::fill(vis.begin(), vis.end(), 0.0);
-        mu[(ad * S + ay) * S + ax] = 1.0;
+        mu[mv.pose(ad, ay, ax)] = 1.0;
         for (int t = 0; t < T; t++) {
             std::fill(nx.begin(), nx.end(), 0.0);
             for (int p = 0; p < P; p++) {

@@ -15,12 +15,16 @@
 // (__shfl_down / __shfl_up with width 32; the edge lanes take 0).  No LDS, no barrier, no atomic.  Every lane of a wave
 // stays in the loop until both of its envs are done (the shuffles read neighbouring lanes), and the half of the last
 // wave that has no env computes on a clamped index and stores nothing.
+// row_mask, layer_seed and store_layer are merlin_grid.h's, shared with k_policy_paths; the layer step is written out.
 #include "merlin_internal.h"
+#include "merlin_grid.h"
 
 #include <vector>
 
 namespace merlin {
 namespace {
+
+using namespace grid;
 
 constexpr int PBLK = 256;            // 8 envs per block
 constexpr int PENVS = PBLK / 32;
@@ -38,22 +42,12 @@ struct PathArgs {
     int16_t *field;          // nullable: int16[n][4][S][S]
 };
 
-// the set bits of row y of direction d's frontier take the value k
-__device__ __forceinline__ void store_layer(int16_t *__restrict__ row, uint32_t f, int k) {
-    while (f) {
-        const int x = __ffs((int)f) - 1;
-        f &= f - 1u;
-        row[x] = (int16_t)k;
-    }
-}
-
 __global__ __launch_bounds__(PBLK) void k_shortest_paths(PathArgs A) {
     const int y = threadIdx.x & 31;
     const int64_t q0 = (int64_t)blockIdx.x * PENVS + (threadIdx.x >> 5);
     const bool live = q0 < A.n;
     const int64_t q = live ? q0 : A.n - 1;  // an env-less half wave computes a copy of the last env, stores nothing
     const int S = A.S;
-    const uint32_t full = S >= 32 ? 0xffffffffu : ((1u << S) - 1u);
 
     int ax, ay, dir, gx, gy;
     int64_t m = q;
@@ -72,8 +66,9 @@ __global__ __launch_bounds__(PBLK) void k_shortest_paths(PathArgs A) {
         gx = A.goal[2 * m];
         gy = A.goal[2 * m + 1];
     }
+    const uint32_t full = row_mask(S);
     const uint32_t free_ = y < S ? ~A.walls[m * A.wstride + y] & full : 0u;
-    const bool goal_in = gx >= 0 && gx < S && gy >= 0 && gy < S;
+    const Goal g = goal_at(gx, gy, S);
     const bool agent_ok = ax >= 0 && ax < S && ay >= 0 && ay < S && dir >= 0 && dir < 4;
     const bool mine = agent_ok && y == ay;  // the lane that holds the agent's row
     const uint32_t abit = mine ? 1u << ax : 0u;
@@ -89,14 +84,9 @@ __global__ __launch_bounds__(PBLK) void k_shortest_paths(PathArgs A) {
         }
     }
 
-    // layer 1: the cell goal - vec(d), vec = (1, 0), (0, 1), (-1, 0), (0, -1)
-    uint32_t F[4], V[4];
+    uint32_t F[4], V[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
-    for (int d = 0; d < 4; d++) {
-        const int sx = gx - ((d == 0) - (d == 2)), sy = gy - ((d == 1) - (d == 3));
-        F[d] = (goal_in && y == sy && sx >= 0 && sx < S) ? (1u << sx) & free_ : 0u;
-        V[d] = 0u;
-    }
+    for (int d = 0; d < 4; d++) F[d] = layer_seed(g, S, d, y, free_);
 
     int res = -1;
     const int half = threadIdx.x & 32;  // bit offset of this env's lanes in a wave-wide ballot
@@ -159,29 +149,29 @@ hipError_t launch_env_optimal_steps(const EnvDev &E, int32_t *dist, int16_t *fie
 // cell is where a forward move from behind lands, the pose one cell back.
 void shortest_paths_host(const uint32_t *walls, const int32_t *goal, const int32_t *agent, int64_t n, int S,
                          int32_t *dist, int16_t *field) {
-    static const int DX[4] = {1, 0, -1, 0}, DY[4] = {0, 1, 0, -1};
+    using namespace grid_host;
     const int P = 4 * S * S;
     std::vector<int> dd(P), queue(P);
     for (int64_t q = 0; q < n; q++) {
-        const uint32_t *w = walls + q * S;
-        auto is_free = [&](int x, int y) { return x >= 0 && x < S && y >= 0 && y < S && !((w[y] >> x) & 1u); };
+        const MapView mv{walls + q * S, S};
         std::fill(dd.begin(), dd.end(), -1);
         int head = 0, tail = 0;
         const int gx = goal[2 * q], gy = goal[2 * q + 1];
-        if (gx >= 0 && gx < S && gy >= 0 && gy < S)
+        if (mv.inside(gx, gy))
             for (int d = 0; d < 4; d++) {
                 const int x = gx - DX[d], y = gy - DY[d];
-                if (is_free(x, y)) {
-                    const int p = (d * S + y) * S + x;
+                if (mv.is_free(x, y)) {
+                    const int p = mv.pose(d, y, x);
                     dd[p] = 1;
                     queue[tail++] = p;
                 }
             }
         while (head < tail) {
             const int p = queue[head++];
-            const int d = p / (S * S), y = (p / S) % S, x = p % S;
-            const int pred[3] = {(((d + 1) & 3) * S + y) * S + x, (((d + 3) & 3) * S + y) * S + x,
-                                 is_free(x - DX[d], y - DY[d]) ? (d * S + (y - DY[d])) * S + (x - DX[d]) : -1};
+            int d, y, x;
+            mv.decode(p, d, y, x);
+            const int pred[3] = {mv.pose((d + 1) & 3, y, x), mv.pose((d + 3) & 3, y, x),
+                                 mv.is_free(x - DX[d], y - DY[d]) ? mv.pose(d, y - DY[d], x - DX[d]) : -1};
             for (int j = 0; j < 3; j++)
                 if (pred[j] >= 0 && dd[pred[j]] < 0) {
                     dd[pred[j]] = dd[p] + 1;
@@ -190,7 +180,7 @@ void shortest_paths_host(const uint32_t *walls, const int32_t *goal, const int32
         }
         if (dist) {
             const int ax = agent[4 * q], ay = agent[4 * q + 1], ad = agent[4 * q + 2];
-            dist[q] = (ad >= 0 && ad < 4 && is_free(ax, ay)) ? dd[(ad * S + ay) * S + ax] : -1;
+            dist[q] = (ad >= 0 && ad < 4 && mv.is_free(ax, ay)) ? dd[mv.pose(ad, ay, ax)] : -1;
         }
         if (field)
             for (int p = 0; p < P; p++) field[q * P + p] = (int16_t)dd[p];

@@ -12,19 +12,23 @@
 // is the depth of p in the tree that hangs from the terminating poses (the free poses in front of the goal whose
 // action is forward); a pose on or leading to a cycle, a forward move into a wall or an action outside {0, 1, 2} has
 // none: -1.  It is k_shortest_paths' backward search (merlin_paths.hip: 32 lanes per map, lane y holds row y, the
-// frontier and visited masks per direction in registers, the vertical moves by shuffles) with an edge kept only where
-// the predecessor's action takes it: per direction three masks L / R / W of the poses that turn left / turn right /
-// move forward, built by the lane from its row of action bytes,
+// frontier and visited masks per direction in registers, the vertical moves by shuffles; the pieces around the
+// layer step are merlin_grid.h's) with an edge kept only where the predecessor's action takes it: per direction three
+// masks L / R / W of the poses that turn left / turn right / move forward, built by the lane from its row of action
+// bytes,
 //   layer 1            F[d] = bit(goal - vec(d)) & free & W[d]
 //   layer k -> k + 1   N[d] = ((F[(d + 3) & 3] & L[d]) | (F[(d + 1) & 3] & R[d]) | (back_d(F[d]) & W[d])) & free & ~V[d]
 // A pose has one successor, so it enters at most one layer -- but for the forward-acting pose in front of the goal,
 // whose front cell also holds a pose (the goal cell is an ordinary cell to stand on): ~V[d] keeps it in layer 1.
 #include "merlin_internal.h"
+#include "merlin_grid.h"
 
 #include <vector>
 
 namespace merlin {
 namespace {
+
+using namespace grid;
 
 constexpr int VBLK = 256;
 
@@ -38,7 +42,7 @@ __global__ __launch_bounds__(VBLK) void k_view_codes(const uint32_t *__restrict_
     const int64_t m = map_index ? (int64_t)map_index[q] : q;
     const int ax = agent[4 * q], ay = agent[4 * q + 1], dir = agent[4 * q + 2];
     const uint32_t *wrow = walls + m * S;
-    bool ok = ax >= 0 && ax < S && ay >= 0 && ay < S && dir >= 0 && dir <= 3;
+    bool ok = in_grid(S, ax, ay) && dir >= 0 && dir <= 3;
     if (ok && ((wrow[ay] >> ax) & 1u)) ok = false;  // no env stands on a wall
     uint32_t out[MERLIN_OBS_WORDS];
 #pragma unroll
@@ -49,15 +53,15 @@ __global__ __launch_bounds__(VBLK) void k_view_codes(const uint32_t *__restrict_
             gx = goal[2 * m];
             gy = goal[2 * m + 1];
         }
-        const bool goal_in = gx >= 0 && gx < S && gy >= 0 && gy < S;
+        const Goal g = goal_at(gx, gy, S);
         uint32_t V[7], vis[7];
         view_mask([&](int y) { return wrow[y]; }, S, ax, ay, dir, V, vis);
         // the goal's view cell: view (vi, vj) shows world agent + (6 - vj) F + (vi - 3) R
-        const int Fx = (dir == 0) - (dir == 2), Fy = (dir == 1) - (dir == 3);
+        const int Fx = dir_x(dir), Fy = dir_y(dir);
         const int Rx = -Fy, Ry = Fx;
-        const int dx = gx - ax, dy = gy - ay;
+        const int dx = g.gx - ax, dy = g.gy - ay;
         const int gvj = 6 - (dx * Fx + dy * Fy), gvi = 3 + (dx * Rx + dy * Ry);
-        const bool ginv = goal_in && gvi >= 0 && gvi < 7 && gvj >= 0 && gvj < 7;
+        const bool ginv = g.in && gvi >= 0 && gvi < 7 && gvj >= 0 && gvj < 7;
         // tile classes: 0 not visible, 1 empty, 2 wall, 3 goal, 4 the agent's own cell (3, 6); nibble vj * 7 + vi
 #pragma unroll
         for (int j = 0; j < 7; j++) {
@@ -87,15 +91,6 @@ __global__ __launch_bounds__(VBLK) void k_view_codes(const uint32_t *__restrict_
 constexpr int PBLK = 256;  // 8 maps per block, as k_shortest_paths
 constexpr int PMAPS = PBLK / 32;
 
-// the set bits of row y of direction d's frontier take the value k
-__device__ __forceinline__ void store_layer(int16_t *__restrict__ row, uint32_t f, int k) {
-    while (f) {
-        const int x = __ffs((int)f) - 1;
-        f &= f - 1u;
-        row[x] = (int16_t)k;
-    }
-}
-
 __global__ __launch_bounds__(PBLK) void k_policy_paths(const uint32_t *__restrict__ walls,
                                                         const int32_t *__restrict__ goal,
                                                         const int8_t *__restrict__ action, int64_t n, int S,
@@ -104,11 +99,10 @@ __global__ __launch_bounds__(PBLK) void k_policy_paths(const uint32_t *__restric
     const int64_t m0 = (int64_t)blockIdx.x * PMAPS + (threadIdx.x >> 5);
     const bool live = m0 < n;
     const int64_t m = live ? m0 : n - 1;  // a map-less half wave computes a copy of the last map, stores nothing
-    const uint32_t full = S >= 32 ? 0xffffffffu : ((1u << S) - 1u);
     const bool row = y < S;
+    const uint32_t full = row_mask(S);
     const uint32_t free_ = row ? ~walls[m * S + y] & full : 0u;
-    const int gx = goal[2 * m], gy = goal[2 * m + 1];
-    const bool goal_in = gx >= 0 && gx < S && gy >= 0 && gy < S;
+    const Goal g = goal_of(goal, m, S);
 
     // this lane's rows: the action masks read, the field set to -1 (overwritten below by the same lane)
     uint32_t L[4], R[4], W[4];
@@ -133,14 +127,10 @@ __global__ __launch_bounds__(PBLK) void k_policy_paths(const uint32_t *__restric
         }
     }
 
-    // layer 1: the cell goal - vec(d), vec = (1, 0), (0, 1), (-1, 0), (0, -1), where the action is forward
-    uint32_t F[4], V[4];
+    // layer 1: the cell goal - vec(d) where the action is forward
+    uint32_t F[4], V[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
-    for (int d = 0; d < 4; d++) {
-        const int sx = gx - ((d == 0) - (d == 2)), sy = gy - ((d == 1) - (d == 3));
-        F[d] = (goal_in && y == sy && sx >= 0 && sx < S) ? (1u << sx) & free_ & W[d] : 0u;
-        V[d] = 0u;
-    }
+    for (int d = 0; d < 4; d++) F[d] = layer_seed(g, S, d, y, free_ & W[d]);
 
     const int kmax = 4 * S * S;
     for (int k = 1; k <= kmax; k++) {
@@ -192,16 +182,15 @@ hipError_t launch_policy_paths(const uint32_t *walls, const int32_t *goal, const
 // forward move into a wall or off the grid), an answered pose or its own path (-1), and unwinds: answer + 1, or -1.
 void policy_paths_host(const uint32_t *walls, const int32_t *goal, const int8_t *action, int64_t n_maps, int S,
                        int16_t *steps) {
-    static const int DX[4] = {1, 0, -1, 0}, DY[4] = {0, 1, 0, -1};
+    using namespace grid_host;
     constexpr int UNSEEN = -2, ON_PATH = -3;
     const int P = 4 * S * S;
     std::vector<int> state(P), path;
     path.reserve(P);
     for (int64_t m = 0; m < n_maps; m++) {
-        const uint32_t *w = walls + m * S;
+        const MapView mv{walls + m * S, S};
         const int8_t *act = action + m * P;
         const int gx = goal[2 * m], gy = goal[2 * m + 1];
-        auto is_free = [&](int x, int y) { return x >= 0 && x < S && y >= 0 && y < S && !((w[y] >> x) & 1u); };
         std::fill(state.begin(), state.end(), UNSEEN);
         for (int p0 = 0; p0 < P; p0++) {
             if (state[p0] != UNSEEN) continue;
@@ -216,17 +205,18 @@ void policy_paths_host(const uint32_t *walls, const int32_t *goal, const int8_t 
                     tail = state[p];
                     break;
                 }
-                const int d = p / (S * S), y = (p / S) % S, x = p % S;
+                int d, y, x;
+                mv.decode(p, d, y, x);
                 const int a = act[p];
                 state[p] = ON_PATH;
                 path.push_back(p);
-                if (!is_free(x, y) || a < 0 || a > 2) {
+                if (!mv.is_free(x, y) || a < 0 || a > 2) {
                     tail = -2;  // the pose itself is the dead end: -1 after the unwind's + 1
                     break;
                 }
                 if (a == 2) {
                     const int fx = x + DX[d], fy = y + DY[d];
-                    if (!is_free(fx, fy)) {
+                    if (!mv.is_free(fx, fy)) {
                         tail = -2;
                         break;
                     }
@@ -234,9 +224,9 @@ void policy_paths_host(const uint32_t *walls, const int32_t *goal, const int8_t 
                         tail = 0;
                         break;
                     }
-                    p = (d * S + fy) * S + fx;
+                    p = mv.pose(d, fy, fx);
                 } else {
-                    p = (((a == 0 ? d + 3 : d + 1) & 3) * S + y) * S + x;
+                    p = mv.pose((a == 0 ? d + 3 : d + 1) & 3, y, x);
                 }
             }
             for (size_t i = path.size(); i-- > 0;) {

@@ -449,12 +449,52 @@ def stream_of(t: torch.Tensor):
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
+def np_ptr(a):
+    """The data pointer of a numpy array for a host entry; None for None."""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _device_maps(name: str, walls, goal, size: int, agent=None, map_index=None, goal_optional: bool = False):
+    """(S, M, n) of the map-analysis wrappers' device tensors: walls int32[M, S], goal int32[M, 2] (or None with
+    goal_optional), agent int32[n, 4] (None: n = M), map_index int32[n] in [0, M) (None: pose q on map q, so M >= n).
+    A wrong dtype or shape: AssertionError; an index outside the maps: MerlinNativeError; contiguity: ptr() checks."""
+    S = int(size)
+    assert walls.dtype == torch.int32 and walls.dim() == 2 and walls.shape[1] == S
+    M = int(walls.shape[0])
+    assert goal_optional if goal is None else (goal.dtype == torch.int32 and goal.shape == (M, 2))
+    if agent is None:
+        return S, M, M
+    n = int(agent.shape[0])
+    assert agent.dtype == torch.int32 and agent.shape == (n, 4)
+    if map_index is None:
+        assert M >= n, "without map_index every pose needs its own map"
+    else:
+        assert map_index.dtype == torch.int32 and map_index.shape == (n,)
+        if n and not (0 <= int(map_index.min()) and int(map_index.max()) < M):
+            raise MerlinNativeError(f"{name}: map_index outside [0, M)")
+    return S, M, n
+
+
+def _host_maps(size: int, walls, goal, *per_map):
+    """(S, M, walls uint32[M, S], goal int32[M, 2], ...) as C-contiguous numpy arrays for a host entry; each of
+    per_map is (array, dtype name, its shape after the leading M), converted and checked the same way."""
+    import numpy as np
+
+    S = int(size)
+    walls = np.ascontiguousarray(np.asarray(walls).astype(np.uint32, copy=False))
+    M = int(walls.shape[0])
+    per_map = ((goal, "int32", (2,)),) + per_map
+    out = [np.ascontiguousarray(a, dtype=dtype) for a, dtype, _ in per_map]
+    assert walls.shape == (M, S) and all(a.shape == (M, *shape) for a, (_, _, shape) in zip(out, per_map))
+    return (S, M, walls, *out)
+
+
 def tile_atlas():
     """uint8[5, 8, 8, 3]: the library's own render of minigrid's 5 reachable tiles."""
     import numpy as np
 
     a = np.zeros((5, 8, 8, 3), dtype=np.uint8)
-    check(lib().merlin_tile_atlas(a.ctypes.data_as(C.c_void_p)), "merlin_tile_atlas")
+    check(lib().merlin_tile_atlas(np_ptr(a)), "merlin_tile_atlas")
     return a
 
 
@@ -467,7 +507,7 @@ def frame_atlas(tile_size: int):
     a = np.zeros((FRAME_TILES, max(ts, 0), max(ts, 0), 3), dtype=np.uint8)
     if a.size == 0:  # the library refuses the size; give it somewhere to not write
         a = np.zeros((1,), dtype=np.uint8)
-    check(lib().merlin_frame_atlas(ts, a.ctypes.data_as(C.c_void_p)), "merlin_frame_atlas")
+    check(lib().merlin_frame_atlas(ts, np_ptr(a)), "merlin_frame_atlas")
     return a
 
 
@@ -484,18 +524,8 @@ def render_frames(walls: torch.Tensor, goal: torch.Tensor | None, agent: torch.T
     """uint8[F, size*ts, size*ts, 3] full-grid frames of recorded states (merlin_render_frames): walls int32[M, size]
     bit rows, goal int32[M, 2], agent int32[F, 4] = (x, y, dir, 0); frame f shows map map_index[f] (int32[F]; None: f,
     then M >= F).  `out`: a contiguous uint8 tensor of that many bytes, any alignment."""
-    S, ts = int(size), int(tile_size)
-    F = int(agent.shape[0])
-    assert agent.dtype == torch.int32 and agent.shape == (F, 4)
-    assert walls.dtype == torch.int32 and walls.dim() == 2 and walls.shape[1] == S
-    M = int(walls.shape[0])
-    assert goal is None or (goal.dtype == torch.int32 and goal.shape == (M, 2))
-    if map_index is None:
-        assert M >= F, "without map_index every frame needs its own map"
-    else:
-        assert map_index.dtype == torch.int32 and map_index.shape == (F,)
-        if F and not (0 <= int(map_index.min()) and int(map_index.max()) < M):
-            raise MerlinNativeError("render_frames: map_index outside [0, M)")
+    ts = int(tile_size)
+    S, _, F = _device_maps("render_frames", walls, goal, size, agent, map_index, goal_optional=True)
     side = S * max(ts, 0)
     if out is None:
         out = torch.empty((F, side, side, 3), dtype=torch.uint8, device=agent.device)
@@ -520,18 +550,7 @@ def shortest_paths(walls: torch.Tensor, goal: torch.Tensor, agent: torch.Tensor,
     grid (merlin_shortest_paths; include/merlin_hip.h has the definition).  walls int32[M, size] bit rows, goal
     int32[M, 2], as MerlinVecEnv.snapshot() gives them.  field=True: (dist, int16[n, 4, size, size]), the distance of
     every pose of each query's map indexed [dir][y][x]."""
-    S = int(size)
-    n = int(agent.shape[0])
-    assert agent.dtype == torch.int32 and agent.shape == (n, 4)
-    assert walls.dtype == torch.int32 and walls.dim() == 2 and walls.shape[1] == S
-    M = int(walls.shape[0])
-    assert goal.dtype == torch.int32 and goal.shape == (M, 2)
-    if map_index is None:
-        assert M >= n, "without map_index every query needs its own map"
-    else:
-        assert map_index.dtype == torch.int32 and map_index.shape == (n,)
-        if n and not (0 <= int(map_index.min()) and int(map_index.max()) < M):
-            raise MerlinNativeError("shortest_paths: map_index outside [0, M)")
+    S, _, n = _device_maps("shortest_paths", walls, goal, size, agent, map_index)
     dist = torch.empty((n,), dtype=torch.int32, device=agent.device)
     fld = torch.empty((n, 4, max(S, 0), max(S, 0)), dtype=torch.int16, device=agent.device) if field else None
     with torch.cuda.device(agent.device), KernelTimer.span("k_shortest_paths", shortest_paths_bytes(n, S, field)):
@@ -545,23 +564,14 @@ def shortest_paths_host(walls, goal, agent, size: int, field: bool = False):
     walls uint32 / int32 [n, size], goal int32[n, 2], agent int32[n, 4]; query q uses map q."""
     import numpy as np
 
-    S = int(size)
-    agent = np.ascontiguousarray(agent, dtype=np.int32)
-    n = int(agent.shape[0])
-    assert agent.shape == (n, 4)
-    walls = np.ascontiguousarray(np.asarray(walls).astype(np.uint32, copy=False))
-    goal = np.ascontiguousarray(goal, dtype=np.int32)
-    assert walls.shape == (n, S) and goal.shape == (n, 2)
+    S, n, walls, goal, agent = _host_maps(size, walls, goal, (agent, "int32", (4,)))
     dist = np.empty((n,), dtype=np.int32)
     fld = np.empty((n, 4, max(S, 0), max(S, 0)), dtype=np.int16) if field else None
-    vp = C.c_void_p
     # a span of its own name: on an idle stream the event pair brackets the host call, and the kernel's statistics
     # stay the kernel's
     with KernelTimer.span("shortest_paths_host", shortest_paths_bytes(n, S, field)):
-        check(lib().merlin_shortest_paths_host(walls.ctypes.data_as(vp), goal.ctypes.data_as(vp),
-                                               agent.ctypes.data_as(vp), n, S, dist.ctypes.data_as(vp),
-                                               fld.ctypes.data_as(vp) if field else None),
-              "merlin_shortest_paths_host")
+        check(lib().merlin_shortest_paths_host(np_ptr(walls), np_ptr(goal), np_ptr(agent), n, S, np_ptr(dist),
+                                               np_ptr(fld)), "merlin_shortest_paths_host")
     return (dist, fld) if field else dist
 
 
@@ -572,18 +582,7 @@ def view_codes(walls: torch.Tensor, goal: torch.Tensor | None, agent: torch.Tens
     int32[M, size] bit rows, goal int32[M, 2] or None, as MerlinVecEnv.snapshot() gives them.  A pose outside the
     grid, on a wall or with dir outside 0..3 gets a zero row and raises DEVERR_BAD_FRAME (tower_errors).  `out`: a
     contiguous int32 tensor of n * 8 elements."""
-    S = int(size)
-    n = int(agent.shape[0])
-    assert agent.dtype == torch.int32 and agent.shape == (n, 4) and agent.is_contiguous()
-    assert walls.dtype == torch.int32 and walls.dim() == 2 and walls.shape[1] == S and walls.is_contiguous()
-    M = int(walls.shape[0])
-    assert goal is None or (goal.dtype == torch.int32 and goal.shape == (M, 2) and goal.is_contiguous())
-    if map_index is None:
-        assert M >= n, "without map_index every query needs its own map"
-    else:
-        assert map_index.dtype == torch.int32 and map_index.shape == (n,) and map_index.is_contiguous()
-        if n and not (0 <= int(map_index.min()) and int(map_index.max()) < M):
-            raise MerlinNativeError("view_codes: map_index outside [0, M)")
+    S, _, n = _device_maps("view_codes", walls, goal, size, agent, map_index, goal_optional=True)
     if out is None:
         out = torch.empty((n, OBS_WORDS), dtype=torch.int32, device=agent.device)
     if out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != n * OBS_WORDS:
@@ -607,11 +606,8 @@ def policy_paths(walls: torch.Tensor, goal: torch.Tensor, action: torch.Tensor, 
     if it never does (merlin_policy_paths; include/merlin_hip.h has the definition).  walls int32[M, size], goal
     int32[M, 2], as MerlinVecEnv.snapshot() gives them.  `out`: a contiguous int16 tensor of that many elements, any
     alignment."""
-    S = int(size)
-    M = int(walls.shape[0])
-    assert walls.dtype == torch.int32 and walls.shape == (M, S) and walls.is_contiguous()
-    assert goal.dtype == torch.int32 and goal.shape == (M, 2) and goal.is_contiguous()
-    assert action.dtype == torch.int8 and action.shape == (M, 4, S, S) and action.is_contiguous()
+    S, M, _ = _device_maps("policy_paths", walls, goal, size)
+    assert action.dtype == torch.int8 and action.shape == (M, 4, S, S)
     if out is None:
         out = torch.empty((M, 4, S, S), dtype=torch.int16, device=walls.device)
     if out.dtype != torch.int16 or not out.is_contiguous() or out.numel() != M * 4 * S * S:
@@ -628,16 +624,10 @@ def policy_paths_host(walls, goal, action, size: int):
     import numpy as np
 
     S = int(size)
-    walls = np.ascontiguousarray(np.asarray(walls).astype(np.uint32, copy=False))
-    M = int(walls.shape[0])
-    goal = np.ascontiguousarray(goal, dtype=np.int32)
-    action = np.ascontiguousarray(action, dtype=np.int8)
-    assert walls.shape == (M, S) and goal.shape == (M, 2) and action.shape == (M, 4, S, S)
+    _, M, walls, goal, action = _host_maps(S, walls, goal, (action, "int8", (4, S, S)))
     steps = np.empty((M, 4, max(S, 0), max(S, 0)), dtype=np.int16)
-    vp = C.c_void_p
     with KernelTimer.span("policy_paths_host", policy_paths_bytes(M, S)):
-        check(lib().merlin_policy_paths_host(walls.ctypes.data_as(vp), goal.ctypes.data_as(vp),
-                                             action.ctypes.data_as(vp), M, S, steps.ctypes.data_as(vp)),
+        check(lib().merlin_policy_paths_host(np_ptr(walls), np_ptr(goal), np_ptr(action), M, S, np_ptr(steps)),
               "merlin_policy_paths_host")
     return steps
 
@@ -705,11 +695,9 @@ def policy_chain(walls: torch.Tensor, goal: torch.Tensor, probs: torch.Tensor, s
     include/merlin_hip.h has the definitions).  walls int32[M, size], goal int32[M, 2], as MerlinVecEnv.snapshot()
     gives them.  `out`: a dict of contiguous float64 tensors to write into.  validate=True reads one reduction back (a
     host sync: pass False inside a graph capture) and raises if a free pose's row is negative, non-finite or zero."""
-    S, T = int(size), int(horizon)
-    M = int(walls.shape[0])
-    assert walls.dtype == torch.int32 and walls.shape == (M, S) and walls.is_contiguous()
-    assert goal.dtype == torch.int32 and goal.shape == (M, 2) and goal.is_contiguous()
-    assert probs.dtype == torch.float32 and probs.shape == (M, 4, S, S, 3) and probs.is_contiguous()
+    T = int(horizon)
+    S, M, _ = _device_maps("policy_chain", walls, goal, size)
+    assert probs.dtype == torch.float32 and probs.shape == (M, 4, S, S, 3)
     if validate and M:
         _check_probs("policy_chain", walls, probs, S, torch)
     res = _f64_outputs("policy_chain", CHAIN_OUTPUTS, outputs, out, dict.fromkeys(CHAIN_OUTPUTS, (M, 4, S, S)),
@@ -729,12 +717,9 @@ def policy_occupancy(walls: torch.Tensor, goal: torch.Tensor, probs: torch.Tenso
     every pose (0 at wall poses) and the probability hit[m, t - 1] that it terminates at action t
     (merlin_policy_occupancy).  An invalid start pose gives NaN rows and raises DEVERR_BAD_FRAME (tower_errors).
     Arguments as policy_chain."""
-    S, T = int(size), int(horizon)
-    M = int(walls.shape[0])
-    assert walls.dtype == torch.int32 and walls.shape == (M, S) and walls.is_contiguous()
-    assert goal.dtype == torch.int32 and goal.shape == (M, 2) and goal.is_contiguous()
-    assert probs.dtype == torch.float32 and probs.shape == (M, 4, S, S, 3) and probs.is_contiguous()
-    assert agent.dtype == torch.int32 and agent.shape == (M, 4) and agent.is_contiguous()
+    T = int(horizon)
+    S, M, n = _device_maps("policy_occupancy", walls, goal, size, agent)
+    assert n == M and probs.dtype == torch.float32 and probs.shape == (M, 4, S, S, 3)
     if validate and M:
         _check_probs("policy_occupancy", walls, probs, S, torch)
     res = _f64_outputs("policy_occupancy", OCCUPANCY_OUTPUTS, outputs, out,
@@ -745,18 +730,6 @@ def policy_occupancy(walls: torch.Tensor, goal: torch.Tensor, probs: torch.Tenso
                                                  ptr(res[0]), ptr(res[1]), stream_of(walls))
         check(rc, "merlin_policy_occupancy")
     return tuple(res)
-
-
-def _chain_host_args(walls, goal, probs, size):
-    import numpy as np
-
-    S = int(size)
-    walls = np.ascontiguousarray(np.asarray(walls).astype(np.uint32, copy=False))
-    M = int(walls.shape[0])
-    goal = np.ascontiguousarray(goal, dtype=np.int32)
-    probs = np.ascontiguousarray(probs, dtype=np.float32)
-    assert walls.shape == (M, S) and goal.shape == (M, 2) and probs.shape == (M, 4, S, S, 3)
-    return S, M, walls, goal, probs
 
 
 def _numpy_f64(name):
@@ -777,17 +750,16 @@ def policy_chain_host(walls, goal, probs, size: int, horizon: int, gamma: float 
     walls uint32 / int32 [M, size], goal int32[M, 2], probs float32[M, 4, size, size, 3]."""
     import numpy as np
 
-    S, M, walls, goal, probs = _chain_host_args(walls, goal, probs, size)
+    S = int(size)
+    _, M, walls, goal, probs = _host_maps(S, walls, goal, (probs, "float32", (4, S, S, 3)))
     if validate and M:
         _check_probs("policy_chain_host", walls, probs, S, np)
     res = _f64_outputs("policy_chain_host", CHAIN_OUTPUTS, outputs, out,
                        dict.fromkeys(CHAIN_OUTPUTS, (M, 4, max(S, 0), max(S, 0))), _numpy_f64("policy_chain_host"))
-    vp = C.c_void_p
     n_out = sum(r is not None for r in res)
     with KernelTimer.span("policy_chain_host", policy_chain_bytes(M, S, n_out)):
-        rc = lib().merlin_policy_chain_host(walls.ctypes.data_as(vp), goal.ctypes.data_as(vp),
-                                            probs.ctypes.data_as(vp), M, S, int(horizon), float(gamma),
-                                            *(None if r is None else r.ctypes.data_as(vp) for r in res))
+        rc = lib().merlin_policy_chain_host(np_ptr(walls), np_ptr(goal), np_ptr(probs), M, S, int(horizon),
+                                            float(gamma), *(np_ptr(r) for r in res))
         check(rc, "merlin_policy_chain_host")
     return tuple(res)
 
@@ -798,21 +770,18 @@ def policy_occupancy_host(walls, goal, probs, agent, size: int, horizon: int, ou
     (merlin_policy_occupancy_host); agent int32[M, 4].  An invalid start pose gives NaN rows (no error flag)."""
     import numpy as np
 
-    S, M, walls, goal, probs = _chain_host_args(walls, goal, probs, size)
-    agent = np.ascontiguousarray(agent, dtype=np.int32)
-    assert agent.shape == (M, 4)
-    T = int(horizon)
+    S, T = int(size), int(horizon)
+    _, M, walls, goal, probs, agent = _host_maps(S, walls, goal, (probs, "float32", (4, S, S, 3)),
+                                                 (agent, "int32", (4,)))
     if validate and M:
         _check_probs("policy_occupancy_host", walls, probs, S, np)
     res = _f64_outputs("policy_occupancy_host", OCCUPANCY_OUTPUTS, outputs, out,
                        {"visits": (M, 4, max(S, 0), max(S, 0)), "hit": (M, max(T, 0))},
                        _numpy_f64("policy_occupancy_host"))
-    vp = C.c_void_p
     nbytes = policy_occupancy_bytes(M, S, T, res[0] is not None, res[1] is not None)
     with KernelTimer.span("policy_occupancy_host", nbytes):
-        rc = lib().merlin_policy_occupancy_host(walls.ctypes.data_as(vp), goal.ctypes.data_as(vp),
-                                                probs.ctypes.data_as(vp), agent.ctypes.data_as(vp), M, S, T,
-                                                *(None if r is None else r.ctypes.data_as(vp) for r in res))
+        rc = lib().merlin_policy_occupancy_host(np_ptr(walls), np_ptr(goal), np_ptr(probs), np_ptr(agent), M, S, T,
+                                                *(np_ptr(r) for r in res))
         check(rc, "merlin_policy_occupancy_host")
     return tuple(res)
 

@@ -21,10 +21,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .envs import MerlinVecEnv
-from .evaluation import SWEEP_SEED_BASE, _per_seed, evaluate_few_shot, evaluate_seeds
-
-_VEC = ((1, 0), (0, 1), (-1, 0), (0, -1))  # DIR_TO_VEC: 0 = +x, 1 = +y, 2 = -x, 3 = -y
+from .evaluation import SWEEP_SEED_BASE, evaluate_few_shot, evaluate_seeds
+from .pose_fields import VEC, seeded_env
 
 
 def optimal_reward(dist, max_steps: int):
@@ -46,17 +44,11 @@ def optimal_paths(seeds, difficulty="mediumhard", size: int = 16, device="cuda",
     One seeded vector env (`difficulty`: one name, or one per seed), one reset and one kernel.  Every evaluate_*
     function plays seed i's map from reset(seed=i), so the result lines up with their outputs task by task."""
     seeds = [int(s) for s in seeds]
-    n = len(seeds)
-    if not n:
+    if not seeds:
         return [], []
-    env = MerlinVecEnv(n, difficulty=_per_seed(difficulty, n), size=size, device=device, max_steps=max_steps, seeds=seeds)
-    try:
-        env.reset()
-        dist = env.optimal_steps()
-        env.errors()
-        return dist.cpu().tolist(), optimal_reward(dist, env.max_steps).cpu().tolist()
-    finally:
-        env.close()
+    with seeded_env(seeds, difficulty, size, device, max_steps) as env:
+        dist, ms = env.optimal_steps(), env.max_steps
+    return dist.cpu().tolist(), optimal_reward(dist, ms).cpu().tolist()
 
 
 def oracle_actions(field: torch.Tensor, walls: torch.Tensor, goal: torch.Tensor, agent: torch.Tensor) -> torch.Tensor:
@@ -68,7 +60,7 @@ def oracle_actions(field: torch.Tensor, walls: torch.Tensor, goal: torch.Tensor,
     dev = field.device
     q = torch.arange(n, device=dev)
     x, y, d = agent[:, 0].long(), agent[:, 1].long(), agent[:, 2].long() & 3
-    vec = torch.tensor(_VEC, dtype=torch.int64, device=dev)
+    vec = torch.tensor(VEC, dtype=torch.int64, device=dev)
     fx, fy = x + vec[d, 0], y + vec[d, 1]
     inside = (fx >= 0) & (fx < S) & (fy >= 0) & (fy < S)
     fxc, fyc = fx.clamp(0, S - 1), fy.clamp(0, S - 1)

@@ -26,24 +26,8 @@ import torch
 
 from . import _native as nat
 from .pathing import optimal_reward
-
-_VEC = ((1, 0), (0, 1), (-1, 0), (0, -1))  # DIR_TO_VEC: 0 = +x, 1 = +y, 2 = -x, 3 = -y
-
-
-def free_cells(walls: torch.Tensor, size: int) -> torch.Tensor:
-    """bool[M, S, S], indexed [y][x]: the cells of walls int32[M, S] (bit x of row y = wall) that are no wall."""
-    x = torch.arange(int(size), device=walls.device, dtype=torch.int64)
-    return ((walls.long().unsqueeze(-1) >> x) & 1) == 0
-
-
-def free_poses(walls: torch.Tensor, size: int):
-    """(agent int32[n, 4] = x, y, dir, 0, map_index int32[n]) on the walls' device: every free pose of every map, in
-    (map, dir, y, x) order -- the row-major order of the [M, 4, S, S] fields."""
-    S = int(size)
-    free = free_cells(walls, S).unsqueeze(1).expand(-1, 4, -1, -1)
-    m, d, y, x = free.nonzero(as_tuple=True)
-    agent = torch.stack([x, y, d, torch.zeros_like(x)], dim=1).to(torch.int32).contiguous()
-    return agent, m.to(torch.int32).contiguous()
+from .pose_fields import (PoseField, distance_field, free_cells, free_poses, maps_for_seeds,  # noqa: F401
+                          over_free_poses, ratio)
 
 
 def _front(t: torch.Tensor, fill):
@@ -57,7 +41,7 @@ def _front(t: torch.Tensor, fill):
 
 
 @dataclass
-class PolicyField:
+class PolicyField(PoseField):
     """All tensors on one device; the [M, 4, S, S] fields are indexed [map][dir][y][x].
 
     walls int32[M, S], goal int32[M, 2]   the maps, as MerlinVecEnv.snapshot() gives them
@@ -79,20 +63,6 @@ class PolicyField:
     codes: torch.Tensor | None = None
     agent: torch.Tensor | None = None
     map_index: torch.Tensor | None = None
-
-    @property
-    def n_maps(self) -> int:
-        return int(self.walls.shape[0])
-
-    def _lookup(self, agent: torch.Tensor):
-        S = self.size
-        agent = agent.to(self.steps.device)
-        if agent.shape != (self.n_maps, 4):
-            raise ValueError(f"one pose per map: expected {self.n_maps}x4, got {tuple(agent.shape)}")
-        x, y, d = agent[:, 0].long(), agent[:, 1].long(), agent[:, 2].long()
-        ok = (x >= 0) & (x < S) & (y >= 0) & (y < S) & (d >= 0) & (d < 4)
-        m = torch.arange(self.n_maps, device=agent.device)
-        return ok, (m, d.clamp(0, 3), y.clamp(0, S - 1), x.clamp(0, S - 1))
 
     def at(self, agent: torch.Tensor):
         """(steps int64[M], dist int64[M]) at the poses agent int32[M, 4] = (x, y, dir, 0), pose m on map m; -1 for a
@@ -148,24 +118,14 @@ class PolicyField:
         err2 = torch.where(solvable, (torch.nan_to_num(self.value.to(f64)) - ret) ** 2,
                            torch.zeros((), dtype=f64, device=st.device))
 
-        def ratio(num, den):
-            num, den = num.to(f64), den.to(f64)
-            return torch.where(den > 0, num / den.clamp(min=1), torch.full_like(num, float("nan")))
-
-        def pooled(v, den):
-            return float(ratio(v.to(f64).sum(), den.sum()))
-
-        def per_map(v, den):
-            return ratio(v.to(f64).sum(dim=(1, 2, 3)), den.sum(dim=(1, 2, 3))).cpu().tolist()
-
         named = {"solved_rate": (solved, solvable), "trapped_rate": (trapped, solvable),
                  "timeout_rate": (timeout, solvable), "spl": (spl, solvable), "excess_steps": (excess, solved),
                  "optimal_action_rate": (optimal, solvable)}
         out = {"n_maps": self.n_maps, "n_free": int(self.free.sum()), "n_solvable": int(solvable.sum()),
                "max_steps": ms, "gamma": float(gamma)}
-        out.update({k: pooled(v, den) for k, (v, den) in named.items()})
-        out["value_rmse"] = pooled(err2, solvable) ** 0.5
-        out["per_map"] = {k: per_map(v, den) for k, (v, den) in named.items()}
+        out.update({k: float(ratio(v, den)) for k, (v, den) in named.items()})
+        out["value_rmse"] = float(ratio(err2, solvable)) ** 0.5
+        out["per_map"] = {k: ratio(v, den, per_map=True).cpu().tolist() for k, (v, den) in named.items()}
         out["per_map"]["n_solvable"] = solvable.sum(dim=(1, 2, 3)).cpu().tolist()
         return out
 
@@ -176,20 +136,13 @@ def field_from_actions(walls: torch.Tensor, goal: torch.Tensor, action: torch.Te
     from the kernels for device tensors (merlin_policy_paths, merlin_shortest_paths), from the library's host
     restatements for CPU tensors."""
     S = int(size)
-    M = int(walls.shape[0])
     free = free_cells(walls, S).unsqueeze(1).expand(-1, 4, -1, -1).contiguous()
     action = torch.where(free, action, torch.full_like(action, -1)).contiguous()
     if walls.is_cuda:
         steps = nat.policy_paths(walls, goal, action, S)
-        _, dist = nat.shortest_paths(walls, goal, torch.zeros((M, 4), dtype=torch.int32, device=walls.device), S,
-                                     field=True)
     else:
-        import numpy as np
-
         steps = torch.from_numpy(nat.policy_paths_host(walls.numpy(), goal.numpy(), action.numpy(), S))
-        _, dist = nat.shortest_paths_host(walls.numpy(), goal.numpy(), np.zeros((M, 4), dtype=np.int32), S, field=True)
-        dist = torch.from_numpy(dist)
-    return PolicyField(S, walls, goal, free, action, value, steps, dist, **extra)
+    return PolicyField(S, walls, goal, free, action, value, steps, distance_field(walls, goal, S), **extra)
 
 
 @torch.no_grad()
@@ -203,23 +156,13 @@ def policy_field(ac, walls: torch.Tensor, goal: torch.Tensor, size: int, chunk: 
     if isinstance(ac, MLPActorCritic) or not hasattr(ac, "act_codes"):
         raise ValueError("the policy field needs a policy that acts on the view codes (act_codes), "
                          f"got {type(ac).__name__}")
-    S = int(size)
-    M = int(walls.shape[0])
-    agent, index = free_poses(walls, S)
-    n = int(agent.shape[0])
-    codes = nat.view_codes(walls, goal, agent, S, map_index=index)
-    act = torch.empty((n,), dtype=torch.int8, device=walls.device)
-    val = torch.empty((n,), dtype=torch.float32, device=walls.device)
-    for i in range(0, n, max(int(chunk), 1)):
-        a, _, v = ac.act_codes(codes[i:i + chunk], deterministic=True)
-        act[i:i + chunk] = a.to(torch.int8)
-        val[i:i + chunk] = v.float()
-    where = (index.long(), agent[:, 2].long(), agent[:, 1].long(), agent[:, 0].long())
-    action = torch.full((M, 4, S, S), -1, dtype=torch.int8, device=walls.device)
-    value = torch.full((M, 4, S, S), float("nan"), dtype=torch.float32, device=walls.device)
-    action[where] = act
-    value[where] = val
-    return field_from_actions(walls, goal, action, value, S, codes=codes, agent=agent, map_index=index)
+    def forward(codes):
+        action, _, value = ac.act_codes(codes, deterministic=True)
+        return action, value
+
+    (action, value), codes, agent, index = over_free_poses(
+        walls, goal, size, chunk, forward, ((torch.int8, (), -1), (torch.float32, (), float("nan"))))
+    return field_from_actions(walls, goal, action, value, size, codes=codes, agent=agent, map_index=index)
 
 
 def policy_field_for_seeds(ac, seeds, difficulty="mediumhard", size: int = 16, device="cuda",
@@ -227,17 +170,5 @@ def policy_field_for_seeds(ac, seeds, difficulty="mediumhard", size: int = 16, d
     """(field, agent int32[n, 4], max_steps): the policy field on the maps evaluate_seeds plays for `seeds` (one
     seeded vector env, one reset, one snapshot; `difficulty`: one name, or one per seed), the start poses, and the
     effective episode limit.  field.predicted_episode(agent, max_steps) lines up with evaluate_seeds seed by seed."""
-    from .envs import MerlinVecEnv
-    from .evaluation import _per_seed
-
-    seeds = [int(s) for s in seeds]
-    n = len(seeds)
-    env = MerlinVecEnv(n, difficulty=_per_seed(difficulty, n), size=size, device=device, max_steps=max_steps, seeds=seeds)
-    try:
-        env.reset()
-        walls, goal, agent = env.snapshot()
-        env.errors()
-        ms = int(env.max_steps)
-    finally:
-        env.close()
+    walls, goal, agent, ms = maps_for_seeds(seeds, difficulty, size, device, max_steps)
     return policy_field(ac, walls, goal, size), agent, ms

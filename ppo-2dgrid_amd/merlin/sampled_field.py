@@ -25,11 +25,11 @@ import torch
 
 from . import _native as nat
 from .pathing import optimal_reward
-from .policy_field import free_cells, free_poses
+from .pose_fields import PoseField, distance_field, free_cells, maps_for_seeds, over_free_poses, ratio
 
 
 @dataclass
-class SampledField:
+class SampledField(PoseField):
     """All tensors on one device; the [M, 4, S, S] fields are indexed [map][dir][y][x].
 
     walls int32[M, S], goal int32[M, 2]   the maps, as MerlinVecEnv.snapshot() gives them
@@ -54,20 +54,6 @@ class SampledField:
     steps: torch.Tensor
     disc: torch.Tensor
     dist: torch.Tensor
-
-    @property
-    def n_maps(self) -> int:
-        return int(self.walls.shape[0])
-
-    def _lookup(self, agent: torch.Tensor):
-        S = self.size
-        agent = agent.to(self.success.device)
-        if agent.shape != (self.n_maps, 4):
-            raise ValueError(f"one pose per map: expected {self.n_maps}x4, got {tuple(agent.shape)}")
-        x, y, d = agent[:, 0].long(), agent[:, 1].long(), agent[:, 2].long()
-        ok = (x >= 0) & (x < S) & (y >= 0) & (y < S) & (d >= 0) & (d < 4)
-        m = torch.arange(self.n_maps, device=agent.device)
-        return ok, (m, d.clamp(0, 3), y.clamp(0, S - 1), x.clamp(0, S - 1))
 
     def at(self, agent: torch.Tensor):
         """(success, ret, steps), float64[M]: the expected result of a sampled episode started in pose agent[m] =
@@ -109,18 +95,13 @@ class SampledField:
                  "return_regret": on(optimal_reward(dist, ms).to(f64) - self.ret)}
         err2 = on((torch.nan_to_num(self.value.to(f64)) - self.disc) ** 2)
 
-        def ratio(num, den):
-            num, den = num.to(f64), den.to(f64)
-            return torch.where(den > 0, num / den.clamp(min=1), torch.full_like(num, float("nan")))
-
-        n_map = solvable.sum(dim=(1, 2, 3))
         out = {"n_maps": self.n_maps, "n_free": int(self.free.sum()), "n_solvable": int(solvable.sum()),
                "max_steps": ms, "gamma": float(self.gamma)}
-        out.update({k: float(ratio(v.sum(), n_map.sum())) for k, v in named.items()})
-        out["value_rmse_sampled"] = float(ratio(err2.sum(), n_map.sum())) ** 0.5
-        out["per_map"] = {k: ratio(v.sum(dim=(1, 2, 3)), n_map).cpu().tolist() for k, v in named.items()}
-        out["per_map"]["value_rmse_sampled"] = ratio(err2.sum(dim=(1, 2, 3)), n_map).sqrt().cpu().tolist()
-        out["per_map"]["n_solvable"] = n_map.cpu().tolist()
+        out.update({k: float(ratio(v, solvable)) for k, v in named.items()})
+        out["value_rmse_sampled"] = float(ratio(err2, solvable)) ** 0.5
+        out["per_map"] = {k: ratio(v, solvable, per_map=True).cpu().tolist() for k, v in named.items()}
+        out["per_map"]["value_rmse_sampled"] = ratio(err2, solvable, per_map=True).sqrt().cpu().tolist()
+        out["per_map"]["n_solvable"] = solvable.sum(dim=(1, 2, 3)).cpu().tolist()
         return out
 
 
@@ -131,21 +112,16 @@ def sampled_field_from_probs(walls: torch.Tensor, goal: torch.Tensor, probs: tor
     the library's host restatements for CPU tensors.  A free pose whose row is negative, non-finite or sums to zero
     raises MerlinNativeError; wall poses' rows are replaced by 1/3 each."""
     S, T = int(size), int(max_steps)
-    M = int(walls.shape[0])
     free = free_cells(walls, S).unsqueeze(1).expand(-1, 4, -1, -1).contiguous()
     probs = torch.where(free.unsqueeze(-1), probs.float(), torch.full_like(probs, 1.0 / 3.0, dtype=torch.float32))
     probs = probs.contiguous()
     value = torch.where(free, value.float(), torch.full_like(value, float("nan"), dtype=torch.float32))
-    zeros = torch.zeros((M, 4), dtype=torch.int32, device=walls.device)
     if walls.is_cuda:
         fields = nat.policy_chain(walls, goal, probs, S, T, gamma=gamma)
-        _, dist = nat.shortest_paths(walls, goal, zeros, S, field=True)
     else:
         fields = nat.policy_chain_host(walls.numpy(), goal.numpy(), probs.numpy(), S, T, gamma=gamma)
         fields = tuple(torch.from_numpy(f) for f in fields)
-        _, dist = nat.shortest_paths_host(walls.numpy(), goal.numpy(), zeros.numpy(), S, field=True)
-        dist = torch.from_numpy(dist)
-    return SampledField(S, T, float(gamma), walls, goal, free, probs, value, *fields, dist)
+    return SampledField(S, T, float(gamma), walls, goal, free, probs, value, *fields, distance_field(walls, goal, S))
 
 
 @torch.no_grad()
@@ -160,24 +136,9 @@ def sampled_field(ac, walls: torch.Tensor, goal: torch.Tensor, size: int, max_st
     if isinstance(ac, MLPActorCritic) or not hasattr(ac, "probs_codes"):
         raise ValueError("the sampled field needs a policy that gives probabilities on the view codes (probs_codes), "
                          f"got {type(ac).__name__}")
-    S = int(size)
-    M = int(walls.shape[0])
-    agent, index = free_poses(walls, S)
-    n = int(agent.shape[0])
-    codes = nat.view_codes(walls, goal, agent, S, map_index=index)
-    pr = torch.empty((n, 3), dtype=torch.float32, device=walls.device)
-    val = torch.empty((n,), dtype=torch.float32, device=walls.device)
-    step = max(int(chunk), 1)
-    for i in range(0, n, step):
-        p, v = ac.probs_codes(codes[i:i + step])
-        pr[i:i + step] = p.float()
-        val[i:i + step] = v.float()
-    where = (index.long(), agent[:, 2].long(), agent[:, 1].long(), agent[:, 0].long())
-    probs = torch.full((M, 4, S, S, 3), 1.0 / 3.0, dtype=torch.float32, device=walls.device)
-    value = torch.full((M, 4, S, S), float("nan"), dtype=torch.float32, device=walls.device)
-    probs[where] = pr
-    value[where] = val
-    return sampled_field_from_probs(walls, goal, probs, value, S, max_steps, gamma)
+    (probs, value), *_ = over_free_poses(walls, goal, size, chunk, ac.probs_codes,
+                                         ((torch.float32, (3,), 1.0 / 3.0), (torch.float32, (), float("nan"))))
+    return sampled_field_from_probs(walls, goal, probs, value, size, max_steps, gamma)
 
 
 def sampled_field_for_seeds(ac, seeds, difficulty="mediumhard", size: int = 16, device="cuda",
@@ -185,17 +146,5 @@ def sampled_field_for_seeds(ac, seeds, difficulty="mediumhard", size: int = 16, 
     """(field, agent int32[n, 4], max_steps): the sampled field on the maps evaluate_seeds plays for `seeds` (one
     seeded vector env, one reset, one snapshot; `difficulty`: one name, or one per seed), the start poses, and the
     effective episode limit.  field.at(agent) is the expected result of a sampled episode of each seed."""
-    from .envs import MerlinVecEnv
-    from .evaluation import _per_seed
-
-    seeds = [int(s) for s in seeds]
-    n = len(seeds)
-    env = MerlinVecEnv(n, difficulty=_per_seed(difficulty, n), size=size, device=device, max_steps=max_steps, seeds=seeds)
-    try:
-        env.reset()
-        walls, goal, agent = env.snapshot()
-        env.errors()
-        ms = int(env.max_steps)
-    finally:
-        env.close()
+    walls, goal, agent, ms = maps_for_seeds(seeds, difficulty, size, device, max_steps)
     return sampled_field(ac, walls, goal, size, ms, gamma=gamma), agent, ms
