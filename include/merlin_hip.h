@@ -951,6 +951,54 @@ int merlin_episode_class_stats(const float *done_dev, const double *ep_return_de
                                const uint8_t *class_dev, int32_t T, int32_t N, int32_t n_classes,
                                double *out_dev, int32_t accumulate, void *stream);
 
+/* ---- finite level sets and level replay ------------------------------------------------------------
+ * Level mode: the context holds a bank of L maps and every map an env takes -- merlin_env_reset, the auto-reset of
+ * every step kernel -- is a level of the bank instead of a generated map.  The k-th map env i takes since the bank
+ * was bound is level l = the smallest index with u <= cdf[l], clamped to L - 1 (numpy searchsorted(cdf, u, 'left'),
+ * clipped), u = the action draw's counter-keyed uniform in (0, 1] of (level_seed, epoch 0, step k, env env_offset + i,
+ * j 0), compared in double: a pure function of (seed, global env index, k, the CDF in force at that reset), whichever
+ * kernel resets.  Level mode reads and writes neither the envs' RNG streams nor their look-ahead maps (a reset never
+ * raises MERLIN_DEVERR_SLOT_EMPTY, merlin_env_refill does nothing); everything after the map is taken is unchanged.
+ *
+ * merlin_env_set_levels: the bank in merlin_env_snapshot's layouts, device memory -- walls_dev uint32[L][size],
+ * goal_dev int32[L][2], agent_dev int32[L][4] (x, y, dir, 0); coordinates are clamped into the grid, the maps'
+ * validity is the caller's -- copied into context-owned buffers, with a uniform CDF (cdf[l] = (l + 1) / L), draw
+ * counters 0 and current levels -1.  L = 0 or a null bank pointer unbinds level mode (the RNG streams and look-ahead
+ * maps are as they were before it).  L outside 1..2^20: MERLIN_E_INVALID; a reseed_each_reset context:
+ * MERLIN_E_UNSUPPORTED.  Allocates and synchronises the stream, like merlin_env_set_difficulties: not capturable, and a
+ * graph captured under an earlier binding must be captured again. */
+int merlin_env_set_levels(merlin_env *env, const uint32_t *walls_dev, const int32_t *goal_dev, const int32_t *agent_dev,
+                          int64_t L, uint64_t level_seed, int64_t env_offset, void *stream);
+/* cdf_dev double[L] (non-decreasing, last entry 1.0) copied into the bound CDF buffer in place, stream-ordered: a graph
+ * captured earlier reads the new weights without a re-capture.  No allocation, no host sync: capturable. */
+int merlin_env_set_level_cdf(merlin_env *env, const double *cdf_dev, void *stream);
+/* cur_dev int32[num_envs] (the level each env is in; -1 before its first map), count_dev uint32[num_envs] (maps taken
+ * since the bank was bound), either nullable.  One kernel: capturable. */
+int merlin_env_levels(merlin_env *env, int32_t *cur_dev, uint32_t *count_dev, void *stream);
+/* A context-bound log the step writes: every later merlin_env_step / merlin_env_act_step launch writes, for each of its
+ * steps t, the level env i is in when it acts -- before the step and its auto-reset -- to log_dev[t * num_envs + i]
+ * (int32[n_steps][num_envs]).  Host state read at launch, no launch of its own: a captured launch keeps the pointer it
+ * was captured with.  NULL (and every new binding or unbinding of a bank): no log.  Before merlin_env_set_levels:
+ * MERLIN_E_INVALID. */
+int merlin_env_set_level_log(merlin_env *env, int32_t *log_dev);
+/* [host] the draw restated on the CPU by the same lines the kernels run: out_host int32[n][k_count], entry (i, k) =
+ * the level of draw k_first + k of global env env_first + i under cdf_host double[L]. */
+int merlin_level_draw_host(uint64_t level_seed, int64_t env_first, int64_t n, int64_t k_first, int64_t k_count,
+                           const double *cdf_host, int64_t L, int32_t *out_host);
+
+/* Per-level scores of a rollout: step (t, i) with level_dev[t][i] in [0, L) adds llrint((double)f * 2^24), f =
+ * fminf(kind == 0 ? fabsf(a) : fmaxf(a, 0), 32768.f), a = adv_dev[t][i] (the un-normalised GAE; kind 0 = the L1 value
+ * loss, 1 = the positive value loss), to sum_dev[level] and 1 to count_dev[level]; other steps are skipped.  int64
+ * sums: the result does not depend on the order of the additions.  accumulate = 0 zeroes both vectors first.
+ * T * N > 2^24 (the sums' headroom), L outside 1..2^20, another kind or a null pointer: MERLIN_E_INVALID.  At most two
+ * launches, 64-bit integer atomics after per-thread and per-block pre-reduction (csrc/merlin_levels.hip), no
+ * allocation, no host sync: capturable. */
+int merlin_level_scores(const float *adv_dev, const int32_t *level_dev, int32_t T, int32_t N, int64_t L, int32_t kind,
+                        int64_t *sum_dev, int64_t *count_dev, int32_t accumulate, void *stream);
+/* [host] the same sums on the CPU. */
+int merlin_level_scores_host(const float *adv_host, const int32_t *level_host, int32_t T, int32_t N, int64_t L,
+                             int32_t kind, int64_t *sum_host, int64_t *count_host, int32_t accumulate);
+
 #ifdef __cplusplus
 }
 #endif

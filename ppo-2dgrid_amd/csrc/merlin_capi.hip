@@ -28,6 +28,9 @@ struct merlin_env {
     // is this buffer once merlin_env_set_difficulties has assigned classes, null (the uniform dev.difficulty) before
     // that and after a NULL assignment
     uint8_t *diff_buf = nullptr;
+    int32_t *level_log = nullptr;  // merlin_env_set_level_log: where the next step launches log the envs' levels
+    // (level mode, merlin_env_set_levels: dev.lv_* are buffers the context owns from one binding to the next or to the
+    // unbinding; a graph captured under a binding reads that binding's buffers)
 };
 
 namespace {
@@ -569,7 +572,7 @@ int merlin_env_destroy(merlin_env *e) {
     merlin::EnvDev &d = e->dev;
     void *ptrs[] = {d.walls, d.agent, d.rng_s, d.rng_i, d.rng_b, d.ep_ret, d.ep_len, d.err, d.visited,
                     d.pg_walls, d.pg_agent, d.pg_rng_s, d.pg_rng_b, d.pg_valid, d.pg_ring, d.rflag, d.bflag,
-                    e->diff_buf};
+                    e->diff_buf, (void *)d.lv_walls, (void *)d.lv_agent, (void *)d.lv_cdf, d.lv_count, d.lv_cur};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     delete e;
@@ -642,6 +645,116 @@ int merlin_env_set_difficulties(merlin_env *e, const int32_t *diff, int32_t n, v
     return MERLIN_OK;
 }
 
+static void free_levels(merlin_env *e) {
+    merlin::EnvDev &d = e->dev;
+    void *ptrs[] = {(void *)d.lv_walls, (void *)d.lv_agent, (void *)d.lv_cdf, d.lv_count, d.lv_cur};
+    for (void *p : ptrs)
+        if (p) (void)hipFree(p);
+    d.lv_n = 0;
+    d.lv_walls = nullptr;
+    d.lv_agent = nullptr;
+    d.lv_cdf = nullptr;
+    d.lv_count = nullptr;
+    d.lv_cur = nullptr;
+    d.lv_seed = 0;
+    d.lv_off = 0;
+    e->level_log = nullptr;
+}
+
+int merlin_env_set_levels(merlin_env *e, const uint32_t *walls, const int32_t *goal, const int32_t *agent, int64_t L,
+                          uint64_t level_seed, int64_t env_offset, void *stream) {
+    if (!e) return fail(MERLIN_E_INVALID, "null env");
+    hipStream_t s = (hipStream_t)stream;
+    const bool unbind = L == 0 || !walls || !goal || !agent;
+    if (!unbind && (L < 1 || L > (1 << 20))) return fail(MERLIN_E_INVALID, "the level count must be in [1, 2^20]");
+    if (!unbind && e->dev.reseed)
+        return fail(MERLIN_E_UNSUPPORTED, "level mode on a reseed_each_reset context (every reset replays one seed)");
+    HIP_TRY(hipStreamSynchronize(s));  // nothing queued on the stream reads the old bank
+    free_levels(e);
+    if (unbind) return MERLIN_OK;
+    merlin::EnvDev &d = e->dev;
+    const size_t n = (size_t)d.n, l = (size_t)L;
+    hipError_t err = hipMalloc((void **)&d.lv_walls, l * d.sp * sizeof(uint32_t));
+    if (err == hipSuccess) err = hipMalloc((void **)&d.lv_agent, l * sizeof(uint4));
+    if (err == hipSuccess) err = hipMalloc((void **)&d.lv_cdf, l * sizeof(double));
+    if (err == hipSuccess) err = hipMalloc((void **)&d.lv_count, n * sizeof(uint32_t));
+    if (err == hipSuccess) err = hipMalloc((void **)&d.lv_cur, n * sizeof(int32_t));
+    if (err == hipSuccess) {
+        d.lv_n = (int)L;
+        d.lv_seed = level_seed;
+        d.lv_off = env_offset;
+        err = merlin::launch_level_bind(d, walls, goal, agent, s);
+    }
+    if (err == hipSuccess) err = hipStreamSynchronize(s);
+    if (err != hipSuccess) {
+        free_levels(e);
+        return hip_fail(err, "merlin_env_set_levels");
+    }
+    return MERLIN_OK;
+}
+
+int merlin_env_set_level_cdf(merlin_env *e, const double *cdf, void *stream) {
+    if (!e || !cdf) return fail(MERLIN_E_INVALID, "null argument");
+    if (!e->dev.lv_n) return fail(MERLIN_E_INVALID, "merlin_env_set_level_cdf before merlin_env_set_levels");
+    HIP_TRY(hipMemcpyAsync(const_cast<double *>(e->dev.lv_cdf), cdf, (size_t)e->dev.lv_n * sizeof(double),
+                           hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_env_levels(merlin_env *e, int32_t *cur, uint32_t *count, void *stream) {
+    if (!e) return fail(MERLIN_E_INVALID, "null env");
+    if (!e->dev.lv_n) return fail(MERLIN_E_INVALID, "merlin_env_levels before merlin_env_set_levels");
+    if (!cur && !count) return MERLIN_OK;
+    HIP_TRY(merlin::launch_env_levels(e->dev, cur, count, (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_env_set_level_log(merlin_env *e, int32_t *log) {
+    if (!e) return fail(MERLIN_E_INVALID, "null env");
+    if (log && !e->dev.lv_n) return fail(MERLIN_E_INVALID, "merlin_env_set_level_log before merlin_env_set_levels");
+    e->level_log = log;
+    return MERLIN_OK;
+}
+
+int merlin_level_draw_host(uint64_t level_seed, int64_t env_first, int64_t n, int64_t k_first, int64_t k_count,
+                           const double *cdf, int64_t L, int32_t *out) {
+    if (n < 0 || k_count < 0) return fail(MERLIN_E_INVALID, "negative count");
+    if (L < 1 || L > (1 << 20)) return fail(MERLIN_E_INVALID, "the level count must be in [1, 2^20]");
+    if (n == 0 || k_count == 0) return MERLIN_OK;
+    if (!cdf || !out) return fail(MERLIN_E_INVALID, "null argument");
+    for (int64_t i = 0; i < n; i++)
+        for (int64_t k = 0; k < k_count; k++)
+            out[i * k_count + k] =
+                merlin::level_draw(cdf, (int)L, level_seed, (uint64_t)(k_first + k), (uint64_t)(env_first + i));
+    return MERLIN_OK;
+}
+
+static int level_scores_args(const float *adv, const int32_t *level, int32_t T, int32_t N, int64_t L, int32_t kind,
+                             const int64_t *sum, const int64_t *count) {
+    if (T < 0 || N < 0) return fail(MERLIN_E_INVALID, "negative step or env count");
+    if ((int64_t)T * N > (1 << 24)) return fail(MERLIN_E_INVALID, "T * N must be <= 2^24 (the int64 sums' headroom)");
+    if (L < 1 || L > (1 << 20)) return fail(MERLIN_E_INVALID, "the level count must be in [1, 2^20]");
+    if (kind != 0 && kind != 1) return fail(MERLIN_E_INVALID, "kind: 0 (L1 value loss) or 1 (positive value loss)");
+    if (!sum || !count || ((int64_t)T * N > 0 && (!adv || !level))) return fail(MERLIN_E_INVALID, "null argument");
+    return MERLIN_OK;
+}
+
+int merlin_level_scores(const float *adv, const int32_t *level, int32_t T, int32_t N, int64_t L, int32_t kind,
+                        int64_t *sum, int64_t *count, int32_t accumulate, void *stream) {
+    const int rc = level_scores_args(adv, level, T, N, L, kind, sum, count);
+    if (rc) return rc;
+    HIP_TRY(merlin::launch_level_scores(adv, level, T, N, (int)L, kind, sum, count, accumulate, (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_level_scores_host(const float *adv, const int32_t *level, int32_t T, int32_t N, int64_t L, int32_t kind,
+                             int64_t *sum, int64_t *count, int32_t accumulate) {
+    const int rc = level_scores_args(adv, level, T, N, L, kind, sum, count);
+    if (rc) return rc;
+    merlin::level_scores_host(adv, level, T, N, (int)L, kind, sum, count, accumulate);
+    return MERLIN_OK;
+}
+
 int merlin_env_reset(merlin_env *e, const uint8_t *mask, uint32_t *obs, void *stream) {
     if (!e) return fail(MERLIN_E_INVALID, "null env");
     // + look-ahead refill; a deeper ring whose refills are the caller's (interval 0) is topped up by the caller too
@@ -679,6 +792,7 @@ int merlin_env_step(merlin_env *e, const int64_t *actions, int32_t n_steps, int6
     const bool refill = !e->seed_slots_full && e->refill_every > 0 && ++e->steps_since_refill >= e->refill_every;
     if (refill) e->steps_since_refill = 0;
     o.no_fallback = e->seed_slots_full || (e->no_fallback && e->refill_every == 0);
+    o.level_log = e->level_log;
     HIP_TRY(merlin::launch_env_step(e->dev, o, refill, (hipStream_t)stream));
     return MERLIN_OK;
 }
@@ -710,6 +824,7 @@ int merlin_env_act_step(merlin_env *e, const float *head_part, int32_t n_parts, 
     const bool refill = !e->seed_slots_full && e->refill_every > 0 && ++e->steps_since_refill >= e->refill_every;
     if (refill) e->steps_since_refill = 0;
     o.no_fallback = e->seed_slots_full || (e->no_fallback && e->refill_every == 0);
+    o.level_log = e->level_log;
     HIP_TRY(merlin::launch_env_step(e->dev, o, refill, (hipStream_t)stream));
     return MERLIN_OK;
 }

@@ -584,6 +584,35 @@ __device__ __forceinline__ bool take_slot(const EnvDev &E, int i, uint32_t (*row
     return true;
 }
 
+// Level mode (merlin_env_set_levels, E.lv_n > 0): an env's next map is a level of the bound bank, drawn from the
+// CDF in force by the counter-keyed uniform of (lv_seed, global env index, the env's map counter) -- no generator, no
+// ring, no RNG stream: the level's rows, agent and goal are copied (64 or 128 B + 16 B), the counter bumped, the level
+// recorded.  The draw is a function of its key and the CDF alone, so every kernel that resets gives the same map.
+template <int SP, int NB>
+__device__ __forceinline__ int take_level(const EnvDev &E, int i, uint32_t (*rows)[NB], int lane, GenOut &g) {
+    const uint32_t k = E.lv_count[i];
+    const int l = level_draw(E.lv_cdf, E.lv_n, E.lv_seed, (uint64_t)k, (uint64_t)(E.lv_off + i));
+    const uint4 *src = reinterpret_cast<const uint4 *>(E.lv_walls + (size_t)l * SP);
+#pragma unroll
+    for (int q = 0; q < SP / 4; q++) {
+        const uint4 v = src[q];
+        rows[4 * q + 0][lane] = v.x;
+        rows[4 * q + 1][lane] = v.y;
+        rows[4 * q + 2][lane] = v.z;
+        rows[4 * q + 3][lane] = v.w;
+    }
+    const uint4 a = E.lv_agent[l];
+    g.ax = a.x & 0xff;
+    g.ay = (a.x >> 8) & 0xff;
+    g.dir = (a.x >> 16) & 3;
+    g.gx = a.z & 0xff;
+    g.gy = (a.z >> 8) & 0xff;
+    g.err = 0u;
+    E.lv_count[i] = k + 1u;
+    E.lv_cur[i] = l;
+    return l;
+}
+
 // Env i's generator: its class in the context's per-env buffer (merlin_env_set_difficulties), or the context's
 // uniform difficulty when there is none.  One lane generates one env's map, so a wave whose envs hold several classes
 // runs their generators one after another (the switch in Grid::generate diverges); any assignment is correct, and one
@@ -609,7 +638,10 @@ template <int SP>
 __device__ __forceinline__ void reset_one(const EnvDev &E, int i, uint32_t (*rows)[BLK], int lane,
                                           uint32_t *__restrict__ obs) {
     GenOut g;
-    take_map<SP, BLK, true>(E, i, rows, lane, g);
+    if (E.lv_n)  // level mode (a kernel-argument scalar: wave-uniform)
+        take_level<SP, BLK>(E, i, rows, lane, g);
+    else
+        take_map<SP, BLK, true>(E, i, rows, lane, g);
     store_rows<SP, BLK>(E, i, rows, lane, E.size);
     E.agent[i] = pack_agent(g.ax, g.ay, g.dir, 0, g.gx, g.gy, g.ax, g.ay, 0);
     E.ep_ret[i] = 0.0;
@@ -765,7 +797,11 @@ __global__ __launch_bounds__(BLK) void k_env_fallback(EnvDev E, uint32_t *__rest
 // generates its map and writes its observation, so this kernel carries no generator (lean registers).
 // ACT: the action drawn from head partials (merlin_env_act_step) -- its own instantiation, so the plain step keeps its
 // registers (the draw's partial loads in flight take ~40 more)
-template <int SP, bool DEFER, bool ACT = false>
+// LV: level mode (E.lv_n > 0, chosen at launch) -- a reset is a bank fetch (take_level), so nothing is deferred and no
+// generator is carried whatever the launch; its own instantiations, so that with level mode off the kernels above are
+// instruction for instruction what they were (as a branch on E.lv_n inside them the fetch cost the lean kernel 8 VGPRs
+// and the benched rollout 0.5 ms).  O.level_log: the level each env acts in, per step
+template <int SP, bool DEFER, bool ACT = false, bool LV = false>
 __global__ __launch_bounds__(SBLK) void k_env_step(EnvDev E, StepOut O) {
     __shared__ uint32_t rows[SP][SBLK];
     const int lane = threadIdx.x;
@@ -783,8 +819,12 @@ __global__ __launch_bounds__(SBLK) void k_env_step(EnvDev E, StepOut O) {
     uint32_t err = 0u;
     bool rows_dirty = false;
     const size_t N = (size_t)E.n;
+    int level = -1;
+    if constexpr (LV) level = O.level_log ? E.lv_cur[i] : -1;
 
     for (int t = 0; t < O.n_steps; t++) {
+        if constexpr (LV)
+            if (O.level_log) O.level_log[(size_t)t * N + i] = level;
         // merlin_env_act_step: the action is drawn here from the acting GEMM's head partials (one launch instead of
         // k_act_draw + this kernel); otherwise read from the caller's actions
         int64_t a;
@@ -844,7 +884,9 @@ __global__ __launch_bounds__(SBLK) void k_env_step(EnvDev E, StepOut O) {
         }
         if (done && O.autoreset) {
             GenOut g;
-            if constexpr (DEFER) {
+            if constexpr (LV) {
+                level = take_level<SP, SBLK>(E, i, rows, lane, g);
+            } else if constexpr (DEFER) {
                 if (!take_slot<SP, SBLK>(E, i, rows, lane, g)) {
                     E.rflag[i] = 1;
                     E.bflag[blockIdx.x] = 1;
@@ -914,7 +956,51 @@ __global__ __launch_bounds__(256) void k_env_full_obs(EnvDev E, uint8_t *__restr
     p[2] = st;
 }
 
+// merlin_env_set_levels: thread j packs level j of a bank in merlin_env_snapshot's layouts (walls uint32[L][S], goal
+// int32[L][2], agent int32[L][4] = x, y, dir, 0) into the bank the resets read (rows padded to SP, the agent format),
+// coordinates clamped into the grid, and writes the uniform CDF entry (j + 1) / L; thread j < n zeroes env j's draw
+// counter and sets its current level to -1
+__global__ __launch_bounds__(256) void k_level_bind(EnvDev E, const uint32_t *__restrict__ walls,
+                                                    const int32_t *__restrict__ goal, const int32_t *__restrict__ agent,
+                                                    uint32_t *__restrict__ lv_walls, uint4 *__restrict__ lv_agent,
+                                                    double *__restrict__ lv_cdf) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    const int S = E.size, L = E.lv_n;
+    if (j < L) {
+        for (int y = 0; y < E.sp; y++) lv_walls[(size_t)j * E.sp + y] = y < S ? walls[(size_t)j * S + y] : 0u;
+        const int ax = min(max(agent[4 * (size_t)j + 0], 0), S - 1), ay = min(max(agent[4 * (size_t)j + 1], 0), S - 1);
+        const int gx = min(max(goal[2 * (size_t)j + 0], 0), S - 1), gy = min(max(goal[2 * (size_t)j + 1], 0), S - 1);
+        lv_agent[j] = pack_agent(ax, ay, agent[4 * (size_t)j + 2] & 3, 0, gx, gy, ax, ay, 0);
+        lv_cdf[j] = (double)(j + 1) / (double)L;
+    }
+    if (j < E.n) {
+        E.lv_count[j] = 0u;
+        E.lv_cur[j] = -1;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_env_levels(EnvDev E, int32_t *__restrict__ cur, uint32_t *__restrict__ count) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= E.n) return;
+    if (cur) cur[i] = E.lv_cur[i];
+    if (count) count[i] = E.lv_count[i];
+}
+
 }  // namespace
+
+hipError_t launch_level_bind(const EnvDev &E, const uint32_t *walls, const int32_t *goal, const int32_t *agent,
+                             hipStream_t s) {
+    const int m = std::max(E.n, E.lv_n);
+    hipLaunchKernelGGL(k_level_bind, dim3((m + 255) / 256), dim3(256), 0, s, E, walls, goal, agent,
+                       const_cast<uint32_t *>(E.lv_walls), const_cast<uint4 *>(E.lv_agent),
+                       const_cast<double *>(E.lv_cdf));
+    return hipGetLastError();
+}
+
+hipError_t launch_env_levels(const EnvDev &E, int32_t *cur, uint32_t *count, hipStream_t s) {
+    hipLaunchKernelGGL(k_env_levels, dim3((E.n + 255) / 256), dim3(256), 0, s, E, cur, count);
+    return hipGetLastError();
+}
 
 template <int SP>
 static hipError_t launch_refill_sp(const EnvDev &E, bool full, hipStream_t s) {
@@ -928,6 +1014,7 @@ static hipError_t launch_refill_sp(const EnvDev &E, bool full, hipStream_t s) {
 }
 
 hipError_t launch_env_refill(const EnvDev &E, bool full, hipStream_t s) {
+    if (E.lv_n) return hipSuccess;  // level mode takes no look-ahead map: nothing to generate
     return E.sp == 16 ? launch_refill_sp<16>(E, full, s) : launch_refill_sp<32>(E, full, s);
 }
 
@@ -944,6 +1031,13 @@ hipError_t launch_env_reset(const EnvDev &E, const uint8_t *mask, uint32_t *obs,
 template <int SP>
 static hipError_t launch_step_sp(const EnvDev &E, const StepOut &O, hipStream_t s) {
     const int nb = (E.n + SBLK - 1) / SBLK;
+    if (E.lv_n) {  // level mode: one kernel for every launch shape (nothing deferred, no generator)
+        if (O.act.part)
+            hipLaunchKernelGGL((k_env_step<SP, true, true, true>), dim3(nb), dim3(SBLK), 0, s, E, O);
+        else
+            hipLaunchKernelGGL((k_env_step<SP, true, false, true>), dim3(nb), dim3(SBLK), 0, s, E, O);
+        return hipGetLastError();
+    }
     if (!O.autoreset) {  // no resets: the lean kernel
         hipLaunchKernelGGL((k_env_step<SP, true>), dim3(nb), dim3(SBLK), 0, s, E, O);
     } else if (O.n_steps == 1) {  // also the fused draw + step (merlin_env_act_step): the generator stays out of the

@@ -28,6 +28,11 @@ namespace merlin {
 //   rflag   uint8[n]        1 = reset due, its slot was empty (single-step launch; k_env_fallback)
 //   bflag   uint8[ceil(n/64)] 1 = some env of that step block (SBLK envs, merlin_env.hip) is flagged
 //   diff    uint8[n]        the env's map generator (MERLIN_* id); null = the uniform `difficulty`
+//   lv_*    level mode (merlin_env_set_levels; lv_n = 0: off): the bank of lv_n maps -- lv_walls uint32[lv_n][SP] (rows
+//           padded to SP as `walls`), lv_agent uint4[lv_n] (agent format above, step 0) -- the sampling CDF
+//           lv_cdf double[lv_n], lv_count uint32[n] (maps env i has taken since the bank was bound: the draw's
+//           counter), lv_cur int32[n] (the level env i is in, -1 before its first map), the draw's key (lv_seed,
+//           lv_off + i); take_level in merlin_env.hip
 struct EnvDev {
     int n, size, sp, difficulty, max_steps;
     int stuck_on, max_stay;
@@ -54,6 +59,14 @@ struct EnvDev {
     uint8_t *rflag;
     uint8_t *bflag;
     const uint8_t *diff;  // per-env generator class uint8[n] (merlin_env_set_difficulties); null: `difficulty` for all
+    int lv_n;  // levels in the bound bank; 0: level mode off (a kernel-argument scalar: the branch is wave-uniform)
+    const uint32_t *lv_walls;
+    const uint4 *lv_agent;
+    const double *lv_cdf;
+    uint32_t *lv_count;
+    int32_t *lv_cur;
+    uint64_t lv_seed;
+    int64_t lv_off;
 };
 
 // step launches between two look-ahead refills (merlin_env_step)
@@ -68,7 +81,7 @@ constexpr int ACT_PARTS_UNROLL = 8;  // head-partial chunks summed with all load
 
 __device__ __forceinline__ float relu_nan(float v) { return v != v ? v : fmaxf(v, 0.0f); }  // torch.relu keeps NaN
 
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {  // splitmix64 finaliser
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t x) {  // splitmix64 finaliser
     x ^= x >> 30;
     x *= 0xbf58476d1ce4e5b9ull;
     x ^= x >> 27;
@@ -78,12 +91,30 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {  // splitmix64 finaliser
 }
 
 // uniform in (0, 1]: 53 random bits of the hash of (seed, epoch, step, env, j)
-__device__ __forceinline__ double uniform01(uint64_t seed, uint64_t epoch, uint64_t step, uint64_t env, int j) {
+__host__ __device__ __forceinline__ double uniform01(uint64_t seed, uint64_t epoch, uint64_t step, uint64_t env, int j) {
     uint64_t x = mix64(seed + 0x9e3779b97f4a7c15ull);
     x = mix64(x ^ (epoch + 0x632be59bd9b4e019ull));
     x = mix64(x ^ (step * 0x8cb92ba72f3d8dd7ull));
     x = mix64(x ^ (env * 0xd6e8feb86659fd93ull + (uint64_t)j));
     return (double)((x >> 11) + 1) * (1.0 / 9007199254740992.0);
+}
+
+// Level mode's draw (merlin_env_set_levels): the k-th map of global env `env` since the bank was bound is the
+// smallest l with u <= cdf[l], clamped to L - 1 (numpy searchsorted(cdf, u, 'left'), clipped), u =
+// uniform01(seed, 0, k, env, 0): at most ceil(log2 L) <= 20 double loads; a NaN entry compares false, so the index
+// stays in [0, L) whatever the CDF holds.  Host and device run these same lines.
+__host__ __device__ __forceinline__ int level_draw(const double *__restrict__ cdf, int L, uint64_t seed, uint64_t k,
+                                                   uint64_t env) {
+    const double u = uniform01(seed, 0ull, k, env, 0);
+    int lo = 0, hi = L - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (u <= cdf[mid])
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    return lo;
 }
 
 // acc[j < A]: the actor's head dot products, acc[ACT_MAXA]: the critic's; biases added here.  Log-softmax, argmax or the
@@ -290,6 +321,7 @@ struct StepOut {
     int32_t *ep_len_out;
     ActIn act;  // act.part != null (n_steps == 1): the action of env i is drawn from the heads' partials first
     int no_fallback;  // single-step launches: no k_env_fallback pass; an empty slot raises MERLIN_DEVERR_SLOT_EMPTY
+    int32_t *level_log;  // level mode (nullable): row t receives the level each env is in when it acts at step t
 };
 
 // Zero `bytes` bytes at p on stream s with a kernel (vector stores).  Every zero-fill of the library goes
@@ -313,6 +345,16 @@ hipError_t launch_env_reset(const EnvDev &E, const uint8_t *mask, uint32_t *obs,
 hipError_t launch_env_step(const EnvDev &E, const StepOut &O, bool refill, hipStream_t s);
 hipError_t launch_env_full_obs(const EnvDev &E, uint8_t *out, hipStream_t s);
 hipError_t launch_env_refill(const EnvDev &E, bool full, hipStream_t s);
+// level mode (merlin_env.hip): pack a bank given in merlin_env_snapshot's layouts into E.lv_walls / E.lv_agent and
+// initialise the CDF (uniform), the draw counters (0) and the current levels (-1); the per-env (level, counter) copy
+hipError_t launch_level_bind(const EnvDev &E, const uint32_t *walls, const int32_t *goal, const int32_t *agent,
+                             hipStream_t s);
+hipError_t launch_env_levels(const EnvDev &E, int32_t *cur, uint32_t *count, hipStream_t s);
+// per-level scores (merlin_levels.hip)
+hipError_t launch_level_scores(const float *adv, const int32_t *level, int T, int N, int L, int kind, int64_t *sum,
+                               int64_t *count, int accumulate, hipStream_t s);
+void level_scores_host(const float *adv, const int32_t *level, int T, int N, int L, int kind, int64_t *sum,
+                       int64_t *count, int accumulate);
 hipError_t upload_atlas(const uint8_t *atlas_host);
 // full-grid RGB frames (merlin_render.hip); atlas: the device copy of the frame atlas of tile size ts
 hipError_t launch_render_frames(const uint32_t *walls, const int32_t *goal, const int32_t *agent,

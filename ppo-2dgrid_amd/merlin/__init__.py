@@ -9,6 +9,7 @@ lib/libmerlin_hip.so (HIP, gfx950); there is no CPU fallback.
 from .actor_critic import CNNActorCritic, MLPActorCritic
 from .envs import MerlinEnv, MerlinVecEnv
 from .few_shot import FewShotAdapter
+from .levels import LevelSampler, LevelSet
 from .ppo import PPO
 from .recording import Recording, record_episodes
 from .rollout_buffer import CodeRolloutBuffer, RolloutBuffer
@@ -18,5 +19,6 @@ from .utils.utils import get_device, set_seed
 from .utils.utils_rl import compute_gae_standard, layer_init
 
 __all__ = ["CNNActorCritic", "MLPActorCritic", "MerlinEnv", "MerlinVecEnv", "FewShotAdapter", "PPO", "CodeRolloutBuffer",
+           "LevelSampler", "LevelSet",
            "Recording", "record_episodes", "RolloutBuffer", "SampledField", "sampled_field", "sampled_field_for_seeds",
            "sampled_field_from_probs", "ScenarioCreator", "get_device", "set_seed", "compute_gae_standard", "layer_init"]

@@ -206,6 +206,13 @@ def lib():
     L.merlin_policy_chain_host.argtypes = [vp, vp, vp, i64, i32, i32, C.c_double, vp, vp, vp, vp]
     L.merlin_policy_occupancy.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp]
     L.merlin_policy_occupancy_host.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp]
+    L.merlin_env_set_levels.argtypes = [vp, vp, vp, vp, i64, C.c_uint64, i64, vp]
+    L.merlin_env_set_level_cdf.argtypes = [vp, vp, vp]
+    L.merlin_env_levels.argtypes = [vp, vp, vp, vp]
+    L.merlin_env_set_level_log.argtypes = [vp, vp]
+    L.merlin_level_draw_host.argtypes = [C.c_uint64, i64, i64, i64, i64, vp, i64, vp]
+    L.merlin_level_scores.argtypes = [vp, vp, i32, i32, i64, i32, vp, vp, i32, vp]
+    L.merlin_level_scores_host.argtypes = [vp, vp, i32, i32, i64, i32, vp, vp, i32]
     check_env_config_layout(L)
     _lib = L
     return L
@@ -263,6 +270,9 @@ EXPORTED_SYMBOLS = (
     "merlin_h3_walk_blocks",
     "merlin_view_codes", "merlin_policy_paths", "merlin_policy_paths_host",
     "merlin_policy_chain", "merlin_policy_chain_host", "merlin_policy_occupancy", "merlin_policy_occupancy_host",
+    "merlin_env_set_levels", "merlin_env_set_level_cdf", "merlin_env_levels", "merlin_env_set_level_log",
+    "merlin_level_draw_host",
+    "merlin_level_scores", "merlin_level_scores_host",
 )
 
 
@@ -2045,3 +2055,62 @@ def episode_class_stats(done, ep_return, ep_length, classes, n_classes, out=None
                                                int(n_classes), ptr(out), int(bool(accumulate)), stream_of(done)),
               "merlin_episode_class_stats")
     return out
+
+
+# ---- finite level sets (merlin/levels.py) -----------------------------------------------------------
+LEVEL_SCORE_KINDS = {"l1_value": 0, "positive_value": 1}
+LEVEL_SCORE_SCALE = float(1 << 24)  # merlin_level_scores' fixed point: a step adds llrint(f * 2^24)
+MAX_LEVELS = 1 << 20
+
+
+def level_draw_host(level_seed: int, env_first: int, n: int, k_first: int, k_count: int, cdf) -> np.ndarray:
+    """int32[n, k_count]: level mode's draws k_first .. k_first + k_count - 1 of the global envs env_first ..
+    env_first + n - 1 under the CDF float64[L], restated on the CPU by the library (merlin_level_draw_host)."""
+    import numpy as np
+
+    cdf = np.ascontiguousarray(np.asarray(cdf, dtype=np.float64))
+    out = np.zeros((int(n), int(k_count)), dtype=np.int32)
+    check(lib().merlin_level_draw_host(int(level_seed) & 0xFFFFFFFFFFFFFFFF, int(env_first), int(n), int(k_first),
+                                       int(k_count), np_ptr(cdf), int(cdf.size), np_ptr(out)),
+          "merlin_level_draw_host")
+    return out
+
+
+def level_scores(adv, levels, L: int, kind="l1_value", sum=None, count=None, accumulate: bool = False):
+    """(sum int64[L], count int64[L]) on the device: the rollout's steps by level (merlin_level_scores).  adv float32
+    [T, N] (the un-normalised GAE), levels int32[T, N]; a step in level l adds llrint(min(|a| or max(a, 0), 32768) *
+    2^24) to sum[l] and 1 to count[l], steps with a level outside [0, L) are skipped.  Integer sums: exact and
+    independent of the order.  accumulate=True adds to the given vectors."""
+    k = LEVEL_SCORE_KINDS[kind] if isinstance(kind, str) else int(kind)
+    if adv.dim() != 2 or adv.dtype != torch.float32 or levels.dtype != torch.int32 or levels.shape != adv.shape:
+        raise ValueError("level_scores: adv float32 [T, N], levels int32 [T, N]")
+    T, N = (int(x) for x in adv.shape)
+    if sum is None or count is None:
+        if accumulate:
+            raise ValueError("level_scores: accumulate needs `sum` and `count`")
+        sum = torch.empty(int(L), dtype=torch.int64, device=adv.device)
+        count = torch.empty(int(L), dtype=torch.int64, device=adv.device)
+    if sum.dtype != torch.int64 or count.dtype != torch.int64 or sum.numel() != int(L) or count.numel() != int(L):
+        raise ValueError("level_scores: sum and count are int64[L]")
+    with torch.cuda.device(adv.device):
+        check(lib().merlin_level_scores(ptr(adv) if T * N else None, ptr(levels) if T * N else None, T, N, int(L), k,
+                                        ptr(sum), ptr(count), int(bool(accumulate)), stream_of(adv)),
+              "merlin_level_scores")
+    return sum, count
+
+
+def level_scores_host(adv, levels, L: int, kind="l1_value", sum=None, count=None, accumulate: bool = False):
+    """level_scores on numpy arrays, summed on the CPU by the library (merlin_level_scores_host)."""
+    import numpy as np
+
+    k = LEVEL_SCORE_KINDS[kind] if isinstance(kind, str) else int(kind)
+    adv = np.ascontiguousarray(np.asarray(adv, dtype=np.float32))
+    levels = np.ascontiguousarray(np.asarray(levels, dtype=np.int32))
+    if adv.ndim != 2 or levels.shape != adv.shape:
+        raise ValueError("level_scores_host: adv float32 [T, N], levels int32 [T, N]")
+    if sum is None or count is None:
+        sum, count = np.zeros(max(int(L), 0), dtype=np.int64), np.zeros(max(int(L), 0), dtype=np.int64)
+    check(lib().merlin_level_scores_host(np_ptr(adv), np_ptr(levels), adv.shape[0], adv.shape[1], int(L), k,
+                                         np_ptr(sum), np_ptr(count), int(bool(accumulate))),
+          "merlin_level_scores_host")
+    return sum, count

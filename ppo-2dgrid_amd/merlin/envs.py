@@ -106,6 +106,8 @@ class MerlinVecEnv:
         self.lookahead_depth = 1  # set_lookahead_depth
         self.step_fallback = True  # set_step_fallback
         self._topup = None  # the stream a refill(stream=...) not yet joined runs on
+        self.level_set = None  # set_levels: the bound bank (None: the envs generate their maps)
+        self.num_levels = 0
         self.class_ids = torch.full((self.num_envs,), nat.DIFFICULTY_IDS[uniform], dtype=torch.uint8,
                                     device=self.device)
         # True once classes are assigned: the kernels then read the context's class buffer instead of the uniform id
@@ -277,6 +279,62 @@ class MerlinVecEnv:
                 int(seed) & 0xFFFFFFFFFFFFFFFF, nat.ptr(epoch), int(step), int(self.env_offset), nat.ptr(action),
                 nat.ptr(logp), nat.ptr(value), nat.ptr(obs_out), nat.ptr(reward), nat.ptr(term), nat.ptr(trunc),
                 nat.ptr(done), nat.ptr(ep_return), nat.ptr(ep_length), self._stream), "merlin_env_act_step")
+
+    # -- finite level sets (merlin/levels.py) --------------------
+    def set_levels(self, level_set, level_seed: int = 0) -> None:
+        """Bind a merlin.levels.LevelSet: from now on every map an env takes -- reset() and every auto-reset -- is a
+        level of the set, drawn from the sampling CDF (uniform until set_level_cdf) by a counter-keyed uniform of
+        (level_seed, env_offset + i, the env's map counter): the same levels whichever kernel resets, and under data
+        parallelism the draws of one process over the concatenated envs.  The look-ahead ring and the envs' RNG streams
+        are neither read nor written.  None unbinds (the streams continue where they were).  Allocates and syncs the
+        current stream; a graph captured before it must be captured again (merlin_env_set_levels)."""
+        self.join_refill()
+        with torch.cuda.device(self.device):
+            if level_set is None:
+                nat.check(self._lib.merlin_env_set_levels(self._h, None, None, None, 0, 0, 0, self._stream),
+                          "merlin_env_set_levels")
+                self.level_set, self.num_levels = None, 0
+                return
+            if level_set.size != self.size:
+                raise ValueError(f"a level set of size {level_set.size} on envs of size {self.size}")
+            ls = level_set.to(self.device)
+            walls, goal, agent = (t.to(torch.int32).contiguous() for t in (ls.walls, ls.goal, ls.agent))
+            nat.check(self._lib.merlin_env_set_levels(self._h, nat.ptr(walls), nat.ptr(goal), nat.ptr(agent), len(ls),
+                                                      int(level_seed) & 0xFFFFFFFFFFFFFFFF, int(self.env_offset),
+                                                      self._stream), "merlin_env_set_levels")
+        self.level_set, self.num_levels = ls, len(ls)
+
+    def set_level_cdf(self, cdf: torch.Tensor) -> None:
+        """The sampling CDF float64[num_levels] (non-decreasing, last entry 1.0; LevelSampler.cdf()) copied into the
+        context's buffer in place, stream-ordered: step launches captured into a graph read the new weights without a
+        re-capture (merlin_env_set_level_cdf)."""
+        cdf = cdf.to(device=self.device, dtype=torch.float64).contiguous()
+        if cdf.numel() != self.num_levels or not self.num_levels:
+            raise ValueError(f"set_level_cdf: {cdf.numel()} entries for {self.num_levels} levels")
+        with torch.cuda.device(self.device):
+            nat.check(self._lib.merlin_env_set_level_cdf(self._h, nat.ptr(cdf), self._stream),
+                      "merlin_env_set_level_cdf")
+
+    def current_levels(self, out: torch.Tensor | None = None, counts: torch.Tensor | None = None) -> torch.Tensor:
+        """int32[N]: the level each env is in, -1 before its first map (merlin_env_levels: one kernel, no host sync,
+        capturable).  `counts` (int32[N], optional) receives the maps each env has taken since set_levels."""
+        if out is None:
+            out = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == self.num_envs
+        assert counts is None or (counts.dtype == torch.int32 and counts.is_contiguous()
+                                  and counts.numel() == self.num_envs)
+        with torch.cuda.device(self.device):
+            nat.check(self._lib.merlin_env_levels(self._h, nat.ptr(out), nat.ptr(counts), self._stream),
+                      "merlin_env_levels")
+        return out
+
+    def set_level_log(self, log: torch.Tensor | None) -> None:
+        """Where the step launches that follow write the level every env acts in: int32[n_steps, N] (one row per step of
+        the launch; merlin_env_set_level_log: host state, no launch -- a launch captured into a graph keeps the tensor it
+        was captured with).  None: no log."""
+        if log is not None:
+            assert log.dtype == torch.int32 and log.is_contiguous() and log.numel() % self.num_envs == 0
+        nat.check(self._lib.merlin_env_set_level_log(self._h, nat.ptr(log)), "merlin_env_set_level_log")
 
     def set_refill_interval(self, every: int) -> None:
         """Refill the used look-ahead map slots every `every` step calls (default 16); 0 leaves the

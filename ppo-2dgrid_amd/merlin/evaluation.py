@@ -12,6 +12,9 @@
 ``sweep_checkpoints`` src/sweep_checkpoints.py:72-100: every ``*.pth`` of a directory on the fixed
                      seeds 200000 + i, ranked by mean reward; checkpoints load through
                      merlin.checkpoints.load_policy (legacy-key remap included).
+``evaluate_levels``  the deterministic episode from every level's start pose of a merlin.levels.LevelSet, read off the
+                     policy field of the set's maps (one batched forward over their free poses, no stepping); equals
+                     evaluate_seeds on a seed-built set.
 ``evaluate_zero_shot`` src/distribution_over_tasks.py:71-120 for many seeds at once: the
                      deterministic episode's reward and length, and its PPO-style loss -- GAE
                      (gamma .995, lambda .95) over the episode with the value after the last step
@@ -92,6 +95,21 @@ def evaluate_seeds(ac, seeds, difficulty="mediumhard", size: int = 16, device="c
         return out
     finally:
         env.close()
+
+
+@torch.no_grad()
+def evaluate_levels(ac, level_set, device="cuda", max_steps: int | None = None, chunk: int = 65536):
+    """(rewards list[float], steps list[int]), entry l the deterministic episode from level l's start pose as
+    evaluate_seeds reports it (the reward at the step the policy terminates, or 0.0 and max_steps when it does not
+    within max_steps, default 4 * size^2): merlin.policy_field's predicted_episode on the set's maps.  Plain envs
+    only: no stuck penalty, no exploration bonus."""
+    from .policy_field import policy_field
+
+    ls = level_set.to(device)
+    ms = int(max_steps) if max_steps else 4 * ls.size * ls.size
+    field = policy_field(ac, ls.walls.contiguous(), ls.goal.contiguous(), ls.size, chunk=chunk)
+    reward, steps = field.predicted_episode(ls.agent.contiguous(), ms)
+    return [float(r) for r in reward.cpu().tolist()], [int(s) for s in steps.cpu().tolist()]
 
 
 @torch.no_grad()

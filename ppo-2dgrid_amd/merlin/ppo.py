@@ -91,7 +91,8 @@ class PPO:
     def __init__(self, env, lr=3e-4, gamma=0.99, lam=0.95, clip_eps=0.2, update_epochs=10,
                  batch_size=2048, minibatch_size=256, vf_coef=0.5, ent_coef=0.01, device="cuda",
                  *, dp: DataParallel | None = None, perm_fn=None, conv1_from_codes: bool = True,
-                 dedup: bool = True, windows: bool = True, rollout_graph: bool = True):
+                 dedup: bool = True, windows: bool = True, rollout_graph: bool = True, level_set=None,
+                 level_sampler=None, level_seed: int = 0):
         self.env = env
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -167,7 +168,7 @@ class PPO:
                 self.use_cnn = True
                 self.obs_shape = (56, 56, 3)
                 self.ac = CNNActorCritic(self.obs_shape, act_dim).to(self.device)
-            self.buf = CodeRolloutBuffer(self.k_steps, N, self.device)
+            self.buf = CodeRolloutBuffer(self.k_steps, N, self.device, levels=level_set is not None)
             self._obs_step = torch.empty((N, 3, 56, 56), dtype=torch.float32, device=self.device)
             self._mb_obs = None
             # look-ahead map refills on a side stream after every step, overlapping the next act
@@ -177,7 +178,8 @@ class PPO:
             self._ring = False
             if self._refill_stream is not None:
                 self.vec.set_refill_interval(0)
-                self.set_map_ring(ROLLOUT_MAP_RING)
+                # a level set: a reset is a bank fetch, there is nothing to look ahead -- no ring, no refills
+                self.set_map_ring(ROLLOUT_MAP_RING and level_set is None)
         else:
             sample_obs, _ = env.reset()
             self.num_envs, self.k_steps, self.batch_size = 1, batch_size, batch_size
@@ -190,6 +192,25 @@ class PPO:
                 self.obs_shape = sample_obs.shape
                 self.ac = CNNActorCritic(self.obs_shape, act_dim).to(self.device)
             self.buffer = RolloutBuffer(batch_size, self.obs_shape, self.device, is_discrete=True)
+        # finite level sets (merlin/levels.py): the env takes its maps from the set, the rollout logs the level every env
+        # acts in, the update scores the levels and hands the sampler's new CDF to the env
+        self.level_set, self.level_sampler = None, None
+        self.level_iteration = 0
+        self.last_level_scores = None  # (sum int64[L], count int64[L]) of the last update, across ranks
+        self.last_level_cdf = None
+        if level_set is not None:
+            if self.vec is None or not self.use_cnn:
+                raise ValueError("a level set needs the vectorised CNN path (a MerlinVecEnv / MerlinEnv)")
+            from .levels import LevelSampler
+
+            self.vec.set_levels(level_set, level_seed)
+            self.level_set = self.vec.level_set
+            self.level_sampler = (level_sampler if level_sampler is not None
+                                  else LevelSampler(len(level_set), "uniform", device=self.device))
+            if self.level_sampler.L != len(level_set):
+                raise ValueError(f"a sampler over {self.level_sampler.L} levels for a set of {len(level_set)}")
+        elif level_sampler is not None:
+            raise ValueError("level_sampler without level_set")
         # every parameter a view of one flat buffer (merlin/fast_step.py: the weight stage reads it with one
         # indexed gather; done before anything captures parameter addresses)
         from .fast_step import flatten_parameters
@@ -303,9 +324,12 @@ class PPO:
         main, side = torch.cuda.current_stream(self.device), self._refill_stream
         every = max(1, int(self.refill_every))
         fallback_was = env.step_fallback
+        levels = buf.levels if self.level_set is not None else None
         if self._ring:
             side = None
             env.set_step_fallback(ROLLOUT_STEP_FALLBACK)
+        elif levels is not None:
+            side = None  # level mode: no look-ahead map to refill, no reset deferred: the same linear chain
         else:
             # refilled after every step and joined before the next: no reset can meet an empty slot, so the step's
             # fallback pass (a graph node per step, ~4 us + its dispatch gap) is left out; errors() would report one
@@ -322,6 +346,8 @@ class PPO:
             # the draw fused into the env step (merlin_env_act_step): one launch fewer per step
             fused = FUSE_ACT_STEP and pack is not None and self.ac.heads_partials_ok(pack)
             for t in range(T):
+                if levels is not None:  # the step logs the level every env acts in at step t: no launch of its own
+                    env.set_level_log(levels[t])
                 if fused:
                     part = self.ac.act_codes_packed(buf.codes[t], pack, step=t, partials=True)
                 else:
@@ -349,6 +375,8 @@ class PPO:
         # the flag is read on the host at launch (a captured graph keeps what it captured): whoever steps the env
         # after the rollout gets the fallback pass back
         env.set_step_fallback(fallback_was)
+        if levels is not None:
+            env.set_level_log(None)
 
     def _capture_rollout(self):
         """Record _rollout_body as one HIP graph (torch.cuda.graph; the env and lookup kernels
@@ -499,12 +527,29 @@ class PPO:
             lv = buf.last_value if last_value is None else last_value
             adv_n, ret = self._advantages(buf.rewards, buf.values, buf.dones, lv, buf.adv, buf.returns)
             self.last_adv_normalized = adv_n  # [T][N], for inspection (the update reads it flat)
+            if self.level_set is not None:
+                self._update_levels()
             B = buf.T * buf.N
             return self._sgd(B, buf.flat_codes, None, buf.actions.reshape(B), buf.logprobs.reshape(B),
                              adv_n.reshape(B), ret.reshape(B))
         states, actions, logp_old, rewards, values_old, dones = self.buffer.get()
         adv_n, ret = self._advantages(rewards, values_old, dones, last_value)
         return self._sgd(states.shape[0], None, states, actions, logp_old, adv_n, ret)
+
+    def _update_levels(self):
+        """Score the levels of the last rollout from its un-normalised advantages (merlin_level_scores), sum the
+        integer vectors across ranks -- every rank then builds the same CDF -- update the sampler and hand its CDF to
+        the env: the next rollout's resets (the captured graph's included) draw from it."""
+        buf, sampler = self.buf, self.level_sampler
+        L = len(self.level_set)
+        s, c = nat.level_scores(buf.adv, buf.levels, L, sampler.score_kind)
+        self.dp.allreduce_sum_(s)
+        self.dp.allreduce_sum_(c)
+        self.level_iteration += 1
+        sampler.update(s, c, self.level_iteration)
+        cdf = sampler.cdf()
+        self.vec.set_level_cdf(cdf)
+        self.last_level_scores, self.last_level_cdf = (s, c), cdf
 
     def _minibatch_obs(self, codes, states, mb_idx):
         if codes is None:

@@ -12,6 +12,8 @@ the vectorised path).
                                                    f32 frame; expanded on demand)
                          actions int64[T][N]; logprobs/values/rewards/dones f32[T][N]
                          adv/returns f32[T][N]; ep_return f64 / ep_length i32 [T][N]
+                         levels  int32[T][N] (level mode only: the level env i was in when
+                                                   it acted at step t)
                        At N=4096, T=256: 33.6 MB codes + 4 MB per f32 field.
 """
 from __future__ import annotations
@@ -45,7 +47,7 @@ class RolloutBuffer:
 
 
 class CodeRolloutBuffer:
-    def __init__(self, T: int, N: int, device):
+    def __init__(self, T: int, N: int, device, levels: bool = False):
         self.T, self.N = int(T), int(N)
         dev = torch.device(device)
         z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=dev)  # noqa: E731
@@ -61,6 +63,7 @@ class CodeRolloutBuffer:
         self.ep_length = z(T, N, dt=torch.int32)
         self.stats = z(3, dt=torch.float64)
         self.last_value = z(N)
+        self.levels = z(T, N, dt=torch.int32) if levels else None
 
     @property
     def flat_codes(self) -> torch.Tensor:

@@ -15,6 +15,13 @@ Same flags and defaults as the reference, plus:
                     per-difficulty mean return / length of the rollout's finished episodes and logs them under
                     train_by_difficulty/<name>/.  Evaluation, the run's name and the checkpoints still follow
                     --difficulty.
+  --num_levels K [--level_seed_base B]   train on a finite set of K levels, the maps of seeds B .. B + K - 1 (the
+                    difficulty, or the --difficulty_mix classes dealt round-robin), instead of endless generation;
+                    --level_file F.npz trains on a saved merlin.levels.LevelSet instead.  --level_replay uniform|plr
+                    samples the levels uniformly or by prioritized level replay (--plr_beta, --plr_rho, --plr_score
+                    l1_value|positive_value).  Each iteration logs levels/train_* (every training level from its start
+                    pose), levels/test_* (--eval_episodes held-out seeds 200000 + i) and their gap, levels/seen,
+                    levels/score_mean and the sampling weights' histogram.  Needs --num_envs > 1.
 Outputs keep the reference's layout: checkpoints/<env_id>_<WxH>_<difficulty>_<ts>/seed_<s>/
 {best_model, ppo_model_<k>k, ppo_model_final}.pth (CNNActorCritic state_dicts with the
 reference's keys) and tb_logs/... scalars (TensorBoard when installed, else scalars.jsonl).
@@ -38,7 +45,7 @@ import torch  # noqa: E402
 from merlin import PPO, ScenarioCreator  # noqa: E402
 from merlin._native import DIFFICULTY_IDS  # noqa: E402
 from merlin.distributed import DataParallel  # noqa: E402
-from merlin.evaluation import evaluate_policy  # noqa: E402
+from merlin.evaluation import SWEEP_SEED_BASE, evaluate_levels, evaluate_policy, evaluate_seeds  # noqa: E402
 from merlin.metrics.ppo_metrics import compute_episode_stats  # noqa: E402
 from merlin.scenario_creator import DEFAULT_CONFIG  # noqa: E402
 from merlin.utils.utils import get_device, set_seed  # noqa: E402
@@ -76,6 +83,13 @@ def parse_args(argv=None):
     p.add_argument("--bonus", type=float, default=0.01)
     p.add_argument("--config", type=str, default=DEFAULT_CONFIG)
     p.add_argument("--difficulty_mix", type=str, default=None, help='e.g. "easy:1,mediumhard:2,hard:1"')
+    p.add_argument("--num_levels", type=int, default=0, help="train on the levels of seeds B .. B + K - 1")
+    p.add_argument("--level_seed_base", type=int, default=0)
+    p.add_argument("--level_file", type=str, default=None, help="a saved merlin.levels.LevelSet (.npz)")
+    p.add_argument("--level_replay", type=str, default="uniform", choices=["uniform", "plr"])
+    p.add_argument("--plr_beta", type=float, default=0.1)
+    p.add_argument("--plr_rho", type=float, default=0.1)
+    p.add_argument("--plr_score", type=str, default="l1_value", choices=["l1_value", "positive_value"])
     return p.parse_args(argv)
 
 
@@ -157,9 +171,30 @@ def train_minigrid(args):
         # rank r's single env is global env r: seed + r, and its action draws are keyed by r
         env = sc.create_env(args.difficulty, seed=args.seed, device=device, env_offset=rank, **size_kw, **flags)
         env.vec.set_base_seed(args.seed)  # create_env ignores its seed, like the reference's
+    level_set = level_sampler = None
+    if args.num_levels or args.level_file:
+        from merlin.levels import LevelSampler, LevelSet
+        from merlin.task_mix import parse_mix
+
+        if args.num_envs <= 1:
+            raise SystemExit("--num_levels / --level_file bind a level set to a vector env: they need --num_envs > 1")
+        if flags["stuck_penalty"] or flags["exploration_bonus"]:
+            raise SystemExit("the levels/* evaluation plays plain episodes: no --stuck_penalty / --exploration_bonus")
+        if args.level_file:
+            level_set = LevelSet.load(args.level_file, device=device)
+            if level_set.size != env.size:
+                raise SystemExit(f"{args.level_file} holds levels of size {level_set.size}, the env is {env.size}")
+        else:
+            classes = list(parse_mix(args.difficulty_mix)) if args.difficulty_mix else [args.difficulty]
+            level_set = LevelSet.from_seeds(
+                range(args.level_seed_base, args.level_seed_base + args.num_levels), size=env.size, device=device,
+                difficulties=[classes[i % len(classes)] for i in range(args.num_levels)])
+        level_sampler = LevelSampler(len(level_set), args.level_replay, beta=args.plr_beta, rho=args.plr_rho,
+                                     score=args.plr_score, device=device)
     agent = PPO(env, lr=args.lr, gamma=args.gamma, lam=args.lam, clip_eps=args.clip_eps,
                 update_epochs=args.update_epochs, batch_size=batch, minibatch_size=args.minibatch_size,
-                vf_coef=args.vf_coef, ent_coef=args.ent_coef, device=device, dp=dp)
+                vf_coef=args.vf_coef, ent_coef=args.ent_coef, device=device, dp=dp, level_set=level_set,
+                level_sampler=level_sampler, level_seed=args.seed)
 
     env_id = sc.get_env_id(args.difficulty)
     size = args.size or int(sc.get_env_size_str(args.difficulty).split("x")[0])
@@ -209,6 +244,23 @@ def train_minigrid(args):
                          ("diagnostics/gradnorm", "gradnorm")):
             writer.add_scalar(tag, update_stats[key], step_count)
         writer.add_scalar("perf/env_steps_per_sec", sps, step_count)
+        if level_set is not None:
+            # the train / test gap: every training level from its start pose against held-out seeds, deterministic
+            tr_r, _ = evaluate_levels(agent.ac, level_set, device=device)
+            te_r, _ = evaluate_seeds(agent.ac, range(SWEEP_SEED_BASE, SWEEP_SEED_BASE + args.eval_episodes),
+                                     difficulty=args.difficulty, size=size, device=device)
+            tr_s, te_s = float(np.mean([r > 0 for r in tr_r])), float(np.mean([r > 0 for r in te_r]))
+            tr_m, te_m = float(np.mean(tr_r)), float(np.mean(te_r))
+            sm = agent.level_sampler
+            seen = int(sm.seen.sum().item())
+            for tag, v in (("levels/train_success", tr_s), ("levels/test_success", te_s), ("levels/gap", tr_s - te_s),
+                           ("levels/train_return", tr_m), ("levels/test_return", te_m),
+                           ("levels/return_gap", tr_m - te_m), ("levels/seen", seen),
+                           ("levels/score_mean", float(sm.score[sm.seen].mean().item()) if seen else 0.0)):
+                writer.add_scalar(tag, v, step_count)
+            writer.add_histogram("levels/sampling_weights", sm.weights().cpu().numpy(), step_count)
+            print(f"[{step_count:>7}] levels | train {tr_s:.3f} / R {tr_m:.3f} | test {te_s:.3f} / R {te_m:.3f} | "
+                  f"gap {tr_s - te_s:+.3f} | seen {seen}/{len(level_set)}", flush=True)
         if by_diff:
             parts = []
             for d, (n, s1, _, sl) in by_diff.items():
