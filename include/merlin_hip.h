@@ -501,6 +501,65 @@ int merlin_tower_window_lut(const int32_t *rows_dev, int64_t n_windows, const fl
 int merlin_minibatch_patch_maps(const int32_t *kid_dev, const int64_t *group_keys_dev, int64_t n_groups,
                                 int64_t n_frames, const int64_t *group_offsets_dev, int32_t n_patches, int32_t *kmap_dev,
                                 int32_t *rmap_dev, int32_t *rep_row_dev, void *stream);
+/* Every minibatch's grouping arrays of an update in one stable sort, one scan and one pass (merlin/windows.py
+ * WindowPlan.update_minibatches(bulk=True) builds the same arrays with torch, element for element).  idxs_dev int64[n]:
+ * the epochs' permutations back to back, n a multiple of period; each period is cut into minibatches of `minibatch`
+ * samples (the last may be short), numbered m = 0 .. nmb - 1 across the epochs.  uid_dev int64[n_samples]: frame id
+ * in [0, n_frames) of each sample.  With G = the number of distinct (minibatch, frame) pairs, in (m, frame) order:
+ *   group_keys[G] = m * n_frames + frame, groups[G] = frame          (both sized n by the caller)
+ *   group_offsets int64[nmb + 2]: [m] = first group of m, [nmb] = G, [nmb + 1] = 1 if an index of idxs or a frame id
+ *                 of uid was out of range (it was then taken as frame 0), else 0
+ *   inv int64[n]: [pos] = position of sample pos's frame among its minibatch's groups
+ *   slot int32[nmb][n_frames]: that position per frame, -1 for a frame absent from the minibatch
+ *   order int32[n]: per minibatch (its samples are sorted positions lo .. hi of the update), the sample positions
+ *                 within the minibatch grouped by frame, ascending within a frame
+ *   offs int32[G + nmb] (sized n + nmb): minibatch m's CSR row starts at offs[group_offsets[m] + m], count + 1 entries
+ * workspace_dev: merlin_plan_minibatches_workspace bytes (-1: bad arguments) of device memory, contents free between
+ * calls; no allocation happens inside.  n and nmb * n_frames must be below 2^31 (MERLIN_E_UNSUPPORTED). */
+int64_t merlin_plan_minibatches_workspace(int64_t n, int64_t period, int64_t minibatch, int64_t n_frames);
+/* The update's frame groups, window / patch / band numbering and the four segmented-sum lists (merlin/dedup.py
+ * FrameGroups, merlin/windows.py WindowPlan and SegmentPlan build the same arrays with torch, element for element; only
+ * rep, any member of its group, is free).  Five stages, each one stable radix sort of (key, entry index) pairs, the run
+ * ids being the numbering and the sorted order the list; a stage's list length comes from the stage before, so the
+ * caller reads counts_dev (int64[8]: frames, mismatch flag, windows, table-row flag, patches, bands, missing-window
+ * flag) after frames, after patches and after bands.  Every stage sorts in workspace_dev, at least
+ * merlin_plan_sort_workspace(list length, key bytes) bytes (frames: n, 8; windows: 16 n_windows, 4; patches:
+ * 9 n_frames, 8; bands: 3 n_patches, 8; dq: 3 n_bands, 4); nothing is allocated inside.
+ *   frames   codes uint32[n][8], mult_host: the 8 hash multipliers (host memory) -> uid int64[n] (groups numbered by
+ *            ascending signed hash), rep int64[n] (first n_frames written), wkey int32[n][25] / pkey uint64[n][9] (the
+ *            representatives' window and patch keys, first n_frames rows), mark / wrank int32[5^9] (the window keys
+ *            present and their ranks), counts[0..2]; counts[1] = 1 when a frame differs from its representative
+ *   windows  -> wid int32[n_frames][25], rows int32[n_windows][16] (counts[3] = 1 when a row >= lut_rows) and the dT2
+ *            list (16 n_windows entries: key = table row, idx = window)
+ *   patches  -> kid int32[n_frames][9], pk uint64[9 n_frames] (the distinct patch keys, counts[4] of them) and the
+ *            patch list (9 n_frames entries)
+ *   bands    -> ub uint64[3 n_patches] (the distinct (row, band) keys, counts[5]) and the band list (3 n_patches)
+ *   dq       -> the dQ list (3 n_bands entries: key = Q row w * 9 + tap, idx = band)
+ * Each list: key / idx int32[entries], fix int32[items][4] and head_fix int32[items] for items of item_len entries
+ * (merlin_segment_sum's fix rows). */
+int64_t merlin_plan_sort_workspace(int64_t n, int32_t key_bytes);
+int merlin_plan_frames(const uint32_t *codes_dev, int64_t n, const uint64_t *mult_host, void *workspace_dev,
+                       int64_t workspace_bytes, int64_t *uid_dev, int64_t *rep_dev, int32_t *wkey_dev,
+                       uint64_t *pkey_dev, int32_t *mark_dev, int32_t *wrank_dev, int64_t *counts_dev, void *stream);
+int merlin_plan_windows(int64_t n_frames, int64_t n_windows, const int32_t *wkey_dev, const int32_t *mark_dev,
+                        const int32_t *wrank_dev, int32_t lut_rows, int64_t item_len, void *workspace_dev,
+                        int64_t workspace_bytes, int32_t *wid_dev, int32_t *rows_dev, int32_t *key_dev,
+                        int32_t *idx_dev, int32_t *fix_dev, int32_t *head_fix_dev, int64_t *counts_dev, void *stream);
+int merlin_plan_patches(int64_t n_frames, const uint64_t *pkey_dev, int64_t item_len, void *workspace_dev,
+                        int64_t workspace_bytes, int32_t *kid_dev, uint64_t *pk_dev, int32_t *key_dev,
+                        int32_t *idx_dev, int32_t *fix_dev, int32_t *head_fix_dev, int64_t *counts_dev, void *stream);
+int merlin_plan_bands(int64_t n_patches, const uint64_t *pk_dev, int64_t item_len, void *workspace_dev,
+                      int64_t workspace_bytes, uint64_t *ub_dev, int32_t *key_dev, int32_t *idx_dev, int32_t *fix_dev,
+                      int32_t *head_fix_dev, int64_t *counts_dev, void *stream);
+int merlin_plan_dq(int64_t n_bands, int64_t n_windows, const uint64_t *ub_dev, const int32_t *mark_dev,
+                   const int32_t *wrank_dev, int64_t item_len, void *workspace_dev, int64_t workspace_bytes,
+                   int32_t *key_dev, int32_t *idx_dev, int32_t *fix_dev, int32_t *head_fix_dev, int64_t *counts_dev,
+                   void *stream);
+int merlin_plan_minibatches(const int64_t *idxs_dev, int64_t n, int64_t period, int64_t minibatch,
+                            const int64_t *uid_dev, int64_t n_samples, int64_t n_frames, void *workspace_dev,
+                            int64_t workspace_bytes, int64_t *group_keys_dev, int64_t *groups_dev, int64_t *inv_dev,
+                            int32_t *slot_dev, int32_t *order_dev, int32_t *offs_dev, int64_t *group_offsets_dev,
+                            void *stream);
 /* window_lut with conv2's bias and ReLU applied as the rows are written: a2w[t][w] = relu(Z2w[t][w] + b2[t]). */
 int merlin_tower_window_lut_bias_relu(const int32_t *rows_dev, int64_t n_windows, const float *tables_dev,
                                       int32_t towers, const float *b2_dev, float *a2w_dev, void *stream);

@@ -1144,6 +1144,136 @@ int merlin_minibatch_patch_maps(const int32_t *kid, const int64_t *group_keys, i
     return MERLIN_OK;
 }
 
+namespace {
+// shared argument rules of the two merlin_plan_minibatches entries; the key span (minibatches * frames) or a code
+int64_t plan_key_span(int64_t n, int64_t period, int64_t mbs, int64_t n_frames, int *rc) {
+    *rc = MERLIN_OK;
+    if (n < 1 || period < 1 || mbs < 1 || n_frames < 1 || n % period) {
+        *rc = fail(MERLIN_E_INVALID, "bad shape: n must be a positive multiple of period");
+        return 0;
+    }
+    const int64_t nmb = (n / period) * ((period + mbs - 1) / mbs);
+    if (n > INT32_MAX || nmb > INT32_MAX / n_frames) {
+        *rc = fail(MERLIN_E_UNSUPPORTED, "more than 2^31 samples or (minibatch, frame) keys");
+        return 0;
+    }
+    return nmb * n_frames;
+}
+}  // namespace
+
+int64_t merlin_plan_sort_workspace(int64_t n, int32_t key_bytes) {
+    if (n < 1 || n > INT32_MAX || (key_bytes != 4 && key_bytes != 8)) {
+        fail(MERLIN_E_INVALID, "bad sort shape");
+        return -1;
+    }
+    const int64_t bytes = merlin::plan_sort_workspace(n, key_bytes);
+    if (bytes < 0) fail(MERLIN_E_HIP, "rocprim scratch size query failed");
+    return bytes;
+}
+
+namespace {
+// a stage's scratch rule: its sort of n pairs with key_bytes-wide keys must fit the workspace
+int plan_stage_args(int64_t n, int32_t key_bytes, const void *ws, int64_t ws_bytes, int64_t item_len, bool ptrs) {
+    if (n < 1 || item_len < 1) return fail(MERLIN_E_INVALID, "bad shape");
+    if (n > INT32_MAX) return fail(MERLIN_E_UNSUPPORTED, "more than 2^31 list entries");
+    if (!ws || !ptrs) return fail(MERLIN_E_INVALID, "null argument");
+    const int64_t need = merlin_plan_sort_workspace(n, key_bytes);
+    if (need < 0) return MERLIN_E_HIP;
+    if (ws_bytes < need) return fail(MERLIN_E_INVALID, "workspace smaller than merlin_plan_sort_workspace");
+    return MERLIN_OK;
+}
+}  // namespace
+
+int merlin_plan_frames(const uint32_t *codes, int64_t n, const uint64_t *mult_host, void *ws, int64_t ws_bytes,
+                       int64_t *uid, int64_t *rep, int32_t *wkey, uint64_t *pkey, int32_t *mark, int32_t *wrank,
+                       int64_t *counts, void *stream) {
+    if (n > INT32_MAX / 25) return fail(MERLIN_E_UNSUPPORTED, "more than 2^31 / 25 frames");
+    const int rc = plan_stage_args(n, 8, ws, ws_bytes, 1,
+                                   codes && mult_host && uid && rep && wkey && pkey && mark && wrank && counts);
+    if (rc != MERLIN_OK) return rc;
+    HIP_TRY(merlin::launch_plan_frames(codes, n, mult_host, ws, ws_bytes, uid, rep, wkey, pkey, mark, wrank, counts,
+                                       (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_plan_windows(int64_t n_frames, int64_t n_windows, const int32_t *wkey, const int32_t *mark,
+                        const int32_t *wrank, int32_t lut_rows, int64_t item_len, void *ws, int64_t ws_bytes,
+                        int32_t *wid, int32_t *rows, int32_t *key, int32_t *idx, int32_t *fix, int32_t *head_fix,
+                        int64_t *counts, void *stream) {
+    if (n_frames < 1 || n_frames > INT32_MAX / 25 || n_windows > 1953125 || lut_rows < 1)
+        return fail(MERLIN_E_INVALID, "bad shape");
+    const int rc = plan_stage_args(n_windows * 16, 4, ws, ws_bytes, item_len,
+                                   wkey && mark && wrank && wid && rows && key && idx && fix && head_fix && counts);
+    if (rc != MERLIN_OK) return rc;
+    HIP_TRY(merlin::launch_plan_windows(n_frames, n_windows, wkey, mark, wrank, lut_rows, item_len, ws, ws_bytes, wid,
+                                        rows, key, idx, fix, head_fix, counts, (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_plan_patches(int64_t n_frames, const uint64_t *pkey, int64_t item_len, void *ws, int64_t ws_bytes,
+                        int32_t *kid, uint64_t *pk, int32_t *key, int32_t *idx, int32_t *fix, int32_t *head_fix,
+                        int64_t *counts, void *stream) {
+    if (n_frames < 1 || n_frames > INT32_MAX / 25) return fail(MERLIN_E_INVALID, "bad shape");
+    const int rc = plan_stage_args(n_frames * 9, 8, ws, ws_bytes, item_len,
+                                   pkey && kid && pk && key && idx && fix && head_fix && counts);
+    if (rc != MERLIN_OK) return rc;
+    HIP_TRY(merlin::launch_plan_patches(n_frames, pkey, item_len, ws, ws_bytes, kid, pk, key, idx, fix, head_fix,
+                                        counts, (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_plan_bands(int64_t n_patches, const uint64_t *pk, int64_t item_len, void *ws, int64_t ws_bytes,
+                      uint64_t *ub, int32_t *key, int32_t *idx, int32_t *fix, int32_t *head_fix, int64_t *counts,
+                      void *stream) {
+    if (n_patches < 1 || n_patches > INT32_MAX / 3) return fail(MERLIN_E_INVALID, "bad shape");
+    const int rc = plan_stage_args(n_patches * 3, 8, ws, ws_bytes, item_len,
+                                   pk && ub && key && idx && fix && head_fix && counts);
+    if (rc != MERLIN_OK) return rc;
+    HIP_TRY(merlin::launch_plan_bands(n_patches, pk, item_len, ws, ws_bytes, ub, key, idx, fix, head_fix, counts,
+                                      (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_plan_dq(int64_t n_bands, int64_t n_windows, const uint64_t *ub, const int32_t *mark, const int32_t *wrank,
+                   int64_t item_len, void *ws, int64_t ws_bytes, int32_t *key, int32_t *idx, int32_t *fix,
+                   int32_t *head_fix, int64_t *counts, void *stream) {
+    if (n_bands < 1 || n_bands > INT32_MAX / 3 || n_windows < 1 || n_windows > 1953125)
+        return fail(MERLIN_E_INVALID, "bad shape");
+    const int rc = plan_stage_args(n_bands * 3, 4, ws, ws_bytes, item_len,
+                                   ub && mark && wrank && key && idx && fix && head_fix && counts);
+    if (rc != MERLIN_OK) return rc;
+    HIP_TRY(merlin::launch_plan_dq(n_bands, n_windows, ub, mark, wrank, item_len, ws, ws_bytes, key, idx, fix,
+                                   head_fix, counts, (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int64_t merlin_plan_minibatches_workspace(int64_t n, int64_t period, int64_t minibatch, int64_t n_frames) {
+    int rc;
+    const int64_t span = plan_key_span(n, period, minibatch, n_frames, &rc);
+    if (rc != MERLIN_OK) return -1;
+    const int64_t bytes = merlin::plan_minibatches_workspace(n, span);
+    if (bytes < 0) fail(MERLIN_E_HIP, "rocprim scratch size query failed");
+    return bytes;
+}
+
+int merlin_plan_minibatches(const int64_t *idxs, int64_t n, int64_t period, int64_t minibatch, const int64_t *uid,
+                            int64_t n_samples, int64_t n_frames, void *workspace, int64_t workspace_bytes,
+                            int64_t *group_keys, int64_t *groups, int64_t *inv, int32_t *slot, int32_t *order,
+                            int32_t *offs, int64_t *group_offsets, void *stream) {
+    int rc;
+    plan_key_span(n, period, minibatch, n_frames, &rc);
+    if (rc != MERLIN_OK) return rc;
+    if (n_samples < 1) return fail(MERLIN_E_INVALID, "bad shape");
+    if (!idxs || !uid || !workspace || !group_keys || !groups || !inv || !slot || !order || !offs || !group_offsets)
+        return fail(MERLIN_E_INVALID, "null argument");
+    if (workspace_bytes < merlin_plan_minibatches_workspace(n, period, minibatch, n_frames))
+        return fail(MERLIN_E_INVALID, "workspace smaller than merlin_plan_minibatches_workspace");
+    HIP_TRY(merlin::launch_plan_minibatches(idxs, n, period, minibatch, uid, n_samples, n_frames, workspace,
+                                            workspace_bytes, group_keys, groups, inv, slot, order, offs,
+                                            group_offsets, (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
 int merlin_tower_window_lut_bias_relu(const int32_t *rows, int64_t nw, const float *tables, int32_t towers,
                                       const float *b2, float *a2w, void *stream) {
     if ((!rows || !tables || !a2w || !b2) && nw > 0) return fail(MERLIN_E_INVALID, "null argument");

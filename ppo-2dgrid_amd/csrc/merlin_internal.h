@@ -427,6 +427,32 @@ hipError_t launch_conv2_lut_bwd(const uint32_t *codes, int64_t n, const float *d
 
 hipError_t launch_patch_maps(const int32_t *kid, const int64_t *gkey, int64_t G, int64_t F, const int64_t *goff, int K,
                              int32_t *kmap, int32_t *rmap, int32_t *rep_row, hipStream_t s);
+// merlin_plan.hip: every minibatch's grouping arrays of an update (scratch bytes for N samples and keys < key_span,
+// -1 on error; the launch returns hipErrorInvalidValue when ws_bytes is short)
+int64_t plan_minibatches_workspace(int64_t N, int64_t key_span);
+hipError_t launch_plan_minibatches(const int64_t *idxs, int64_t N, int64_t P, int64_t mbs, const int64_t *uid,
+                                   int64_t B0, int64_t F, void *ws, int64_t ws_bytes, int64_t *gkey, int64_t *gall,
+                                   int64_t *inv, int32_t *slot, int32_t *order, int32_t *offs, int64_t *goff,
+                                   hipStream_t s);
+// the update's frames, windows, patches, bands and segmented-sum lists (include/merlin_hip.h merlin_plan_*); every
+// stage sorts n (key, entry) pairs in plan_sort_workspace(n, key bytes) bytes of the caller's scratch
+int64_t plan_sort_workspace(int64_t n, int key_bytes);
+hipError_t launch_plan_frames(const uint32_t *codes, int64_t B, const uint64_t *mult, void *ws, int64_t ws_bytes,
+                              int64_t *uid, int64_t *rep, int32_t *wkey, uint64_t *pkey, int32_t *mark,
+                              int32_t *wrank, int64_t *counts, hipStream_t st);
+hipError_t launch_plan_windows(int64_t F, int64_t nw, const int32_t *wkey, const int32_t *mark, const int32_t *wrank,
+                               int lut_rows, int64_t L, void *ws, int64_t ws_bytes, int32_t *wid, int32_t *rows,
+                               int32_t *key, int32_t *idx, int32_t *fix, int32_t *head_fix, int64_t *counts,
+                               hipStream_t st);
+hipError_t launch_plan_patches(int64_t F, const uint64_t *pkey, int64_t L, void *ws, int64_t ws_bytes, int32_t *kid,
+                               uint64_t *pk, int32_t *key, int32_t *idx, int32_t *fix, int32_t *head_fix,
+                               int64_t *counts, hipStream_t st);
+hipError_t launch_plan_bands(int64_t K, const uint64_t *pk, int64_t L, void *ws, int64_t ws_bytes, uint64_t *ub,
+                             int32_t *key, int32_t *idx, int32_t *fix, int32_t *head_fix, int64_t *counts,
+                             hipStream_t st);
+hipError_t launch_plan_dq(int64_t nb, int64_t nw, const uint64_t *ub, const int32_t *mark, const int32_t *wrank,
+                          int64_t L, void *ws, int64_t ws_bytes, int32_t *key, int32_t *idx, int32_t *fix,
+                          int32_t *head_fix, int64_t *counts, hipStream_t st);
 hipError_t launch_window_lut(const int32_t *rows, int64_t nw, const float *tab, int T, float *Z2w, hipStream_t s,
                              const float *b2 = nullptr);
 hipError_t launch_window_conv3(const float *Q, int64_t nw, const int32_t *wid, const int64_t *groups, int64_t n,

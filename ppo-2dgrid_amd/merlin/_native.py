@@ -116,6 +116,16 @@ def lib():
     L.merlin_tower_window_conv3.argtypes = [vp, i64, vp, vp, i64, vp, i32, vp, vp]
     L.merlin_tower_window_lut_bias_relu.argtypes = [vp, i64, vp, i32, vp, vp, vp]
     L.merlin_minibatch_patch_maps.argtypes = [vp, vp, i64, i64, vp, i32, vp, vp, vp, vp]
+    L.merlin_plan_sort_workspace.argtypes = [i64, i32]
+    L.merlin_plan_sort_workspace.restype = i64
+    L.merlin_plan_frames.argtypes = [vp, i64, u64p, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.merlin_plan_windows.argtypes = [i64, i64, vp, vp, vp, i32, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.merlin_plan_patches.argtypes = [i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.merlin_plan_bands.argtypes = [i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.merlin_plan_dq.argtypes = [i64, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp]
+    L.merlin_plan_minibatches_workspace.argtypes = [i64, i64, i64, i64]
+    L.merlin_plan_minibatches_workspace.restype = i64
+    L.merlin_plan_minibatches.argtypes = [vp, i64, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.merlin_tower_window_conv3_bits.argtypes = [vp, i64, vp, vp, i64, vp, i32, vp, vp, vp, vp]
     L.merlin_tower_window_conv3_reuse.argtypes = [vp, i64, vp, vp, i64, vp, i32, vp, vp, vp, vp, i32, vp]
     L.merlin_tower_all_windows.restype = i64
@@ -273,6 +283,8 @@ EXPORTED_SYMBOLS = (
     "merlin_env_set_levels", "merlin_env_set_level_cdf", "merlin_env_levels", "merlin_env_set_level_log",
     "merlin_level_draw_host",
     "merlin_level_scores", "merlin_level_scores_host",
+    "merlin_plan_minibatches_workspace", "merlin_plan_minibatches", "merlin_plan_sort_workspace",
+    "merlin_plan_frames", "merlin_plan_windows", "merlin_plan_patches", "merlin_plan_bands", "merlin_plan_dq",
 )
 
 
@@ -1137,6 +1149,115 @@ def minibatch_patch_maps(kid, group_keys, num_frames, group_offsets, nmb, num_pa
                                             ptr(kmap), ptr(rmap), ptr(rep_row), stream_of(group_keys)),
           "merlin_minibatch_patch_maps")
     return kmap, rep_row
+
+
+class PlanWorkspace:
+    """Device scratch of the native planner (merlin_plan_*): one torch-allocated byte tensor per device, grown when
+    a call needs more and otherwise reused from update to update (the planner itself allocates nothing)."""
+
+    def __init__(self):
+        self.buf = None
+
+    def get(self, nbytes: int, device) -> torch.Tensor:
+        if self.buf is None or self.buf.device != device or self.buf.numel() < nbytes:
+            self.buf = None  # release before growing
+            self.buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+        return self.buf
+
+
+WINDOW_KEYS = 5 ** 9  # 3x3 windows of 5 tile classes
+
+
+class PlanLists:
+    """The native planner's phase 1 (merlin_plan_frames / _windows / _patches / _bands / _dq), stage by stage; the
+    caller (merlin.windows.native_plan) reads `counts` between the stages whose list lengths it needs."""
+
+    def __init__(self, codes, mult, workspace: PlanWorkspace):
+        assert codes.dtype == torch.int32 and codes.dim() == 2 and codes.shape[1] == OBS_WORDS
+        self.codes, self.ws, self.dev = codes.contiguous(), workspace, codes.device
+        self.B = B = int(codes.shape[0])
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.dev)  # noqa: E731
+        self.uid, self.rep = e(B, torch.int64), e(B, torch.int64)
+        self.wkey, self.pkey = e((B, 25), torch.int32), e((B, 9), torch.int64)
+        self.mark, self.wrank = e(WINDOW_KEYS, torch.int32), e(WINDOW_KEYS, torch.int32)
+        self.counts = e(8, torch.int64)
+        m = (C.c_uint64 * 8)(*[int(x) & (2 ** 64 - 1) for x in mult])
+        ws = self._scratch(B, 8)
+        check(lib().merlin_plan_frames(ptr(self.codes), B, m, ptr(ws), ws.numel(), ptr(self.uid), ptr(self.rep),
+                                       ptr(self.wkey), ptr(self.pkey), ptr(self.mark), ptr(self.wrank),
+                                       ptr(self.counts), stream_of(codes)), "merlin_plan_frames")
+
+    def _scratch(self, n, key_bytes):
+        nbytes = int(lib().merlin_plan_sort_workspace(int(n), key_bytes))
+        if nbytes < 0:
+            check(E_INVALID, "merlin_plan_sort_workspace")
+        return self.ws.get(nbytes, self.dev)
+
+    def _list(self, n, L):
+        nitems = (n + L - 1) // L
+        e = lambda shape: torch.empty(shape, dtype=torch.int32, device=self.dev)  # noqa: E731
+        return e(n), e(n), e((nitems, 4)), e(nitems)
+
+    def windows(self, F, nw, L):
+        wid, rows = (torch.empty((F, 25), dtype=torch.int32, device=self.dev),
+                     torch.empty((nw, 16), dtype=torch.int32, device=self.dev))
+        lst = self._list(nw * 16, L)
+        ws = self._scratch(nw * 16, 4)
+        check(lib().merlin_plan_windows(F, nw, ptr(self.wkey), ptr(self.mark), ptr(self.wrank), LUT2_ROWS, L, ptr(ws),
+                                        ws.numel(), ptr(wid), ptr(rows), *map(ptr, lst), ptr(self.counts),
+                                        stream_of(self.codes)), "merlin_plan_windows")
+        return wid, rows, lst
+
+    def patches(self, F, L):
+        kid = torch.empty((F, 9), dtype=torch.int32, device=self.dev)
+        self.pk = torch.empty(F * 9, dtype=torch.int64, device=self.dev)
+        lst = self._list(F * 9, L)
+        ws = self._scratch(F * 9, 8)
+        check(lib().merlin_plan_patches(F, ptr(self.pkey), L, ptr(ws), ws.numel(), ptr(kid), ptr(self.pk),
+                                        *map(ptr, lst), ptr(self.counts), stream_of(self.codes)),
+              "merlin_plan_patches")
+        return kid, lst
+
+    def bands(self, K, L):
+        self.ub = torch.empty(K * 3, dtype=torch.int64, device=self.dev)
+        lst = self._list(K * 3, L)
+        ws = self._scratch(K * 3, 8)
+        check(lib().merlin_plan_bands(K, ptr(self.pk), L, ptr(ws), ws.numel(), ptr(self.ub), *map(ptr, lst),
+                                      ptr(self.counts), stream_of(self.codes)), "merlin_plan_bands")
+        return lst
+
+    def dq(self, nb, nw, L):
+        lst = self._list(nb * 3, L)
+        ws = self._scratch(nb * 3, 4)
+        check(lib().merlin_plan_dq(nb, nw, ptr(self.ub), ptr(self.mark), ptr(self.wrank), L, ptr(ws), ws.numel(),
+                                   *map(ptr, lst), ptr(self.counts), stream_of(self.codes)), "merlin_plan_dq")
+        return lst
+
+
+def plan_minibatches(idxs, period, minibatch_size, uid, num_frames, workspace: PlanWorkspace):
+    """merlin_plan_minibatches: (group_keys int64 [n], groups int64 [n], inv int64 [n], slot int32 [nmb, F], order
+    int32 [n], offs int32 [n + nmb], group_offsets int64 [nmb + 2]) of the update's n samples idxs (the epochs'
+    permutations back to back); the first G = group_offsets[nmb] entries of group_keys / groups and the first G + nmb
+    of offs are written.  No host read here."""
+    n, P, mbs, F = int(idxs.numel()), int(period), int(minibatch_size), int(num_frames)
+    assert idxs.dtype == torch.int64 and uid.dtype == torch.int64 and idxs.dim() == 1 and uid.dim() == 1
+    dev = idxs.device
+    nbytes = int(lib().merlin_plan_minibatches_workspace(n, P, mbs, F))
+    if nbytes < 0:
+        check(E_INVALID, "merlin_plan_minibatches_workspace")
+    ws = workspace.get(nbytes, dev)
+    nmb = (n // P) * ((P + mbs - 1) // mbs)
+    gkey = torch.empty(n, dtype=torch.int64, device=dev)
+    groups = torch.empty(n, dtype=torch.int64, device=dev)
+    inv = torch.empty(n, dtype=torch.int64, device=dev)
+    slot = torch.empty((nmb, F), dtype=torch.int32, device=dev)
+    order = torch.empty(n, dtype=torch.int32, device=dev)
+    offs = torch.empty(n + nmb, dtype=torch.int32, device=dev)
+    goff = torch.empty(nmb + 2, dtype=torch.int64, device=dev)
+    check(lib().merlin_plan_minibatches(ptr(idxs), n, P, mbs, ptr(uid), int(uid.numel()), F, ptr(ws), ws.numel(),
+                                        ptr(gkey), ptr(groups), ptr(inv), ptr(slot), ptr(order), ptr(offs), ptr(goff),
+                                        stream_of(idxs)), "merlin_plan_minibatches")
+    return gkey, groups, inv, slot, order, offs, goff
 
 
 def window_conv3_copy_masks(Y3, bits, rep_row):

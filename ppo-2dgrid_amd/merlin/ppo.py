@@ -569,15 +569,16 @@ class PPO:
         use_codes = codes is not None and self.conv1_from_codes
         groups = plan = None
         if use_codes and self.dedup:
+            from . import windows as W
             from .dedup import FrameGroups
 
-            groups = FrameGroups(codes)
+            native = self.windows and W.NATIVE_PLAN and codes.is_cuda  # groups and plan as native launches
+            groups, plan = W.WindowPlan.native(codes) if native else (FrameGroups(codes), None)
             if not groups.ok:  # a 64-bit hash collision: evaluate every sample this update
                 groups = None
             elif self.windows:
-                from .windows import WindowPlan
-
-                plan = WindowPlan(codes, groups)
+                if plan is None:
+                    plan = W.WindowPlan(codes, groups)
                 self.last_num_windows = plan.num_windows
         distinct = 0
         host_mb = []

@@ -41,6 +41,7 @@ frames are its distinct observations (merlin/dedup.py); fc1 and the heads run on
 from __future__ import annotations
 
 import contextlib
+import os
 import threading
 
 import torch
@@ -241,6 +242,39 @@ class MinibatchWindows:
         return self._offs
 
 
+class _BulkViews:
+    """One minibatch of the native bulk builder (WindowPlan._native_minibatches): MinibatchWindows' attributes plus
+    kmap / rep_row / n_reps, each a view of an update-wide array.  The views are cut on first use, when the
+    minibatch's step is queued: the host runs ahead of the GPU from the first step on, while all of an update's
+    views cut up front are host work under an idle GPU."""
+
+    _NAMES = ("groups", "inv", "slot", "order", "offs", "kmap", "rep_row", "n_reps")
+
+    def __init__(self, arrays, m, g0, c, lo, hi):
+        self._cut = (arrays, m, g0, c, lo, hi)
+
+    def __getattr__(self, name):  # only reached while the views are not cut yet
+        if name not in _BulkViews._NAMES:
+            raise AttributeError(name)
+        (gall, inv, slot, order, offs, kmap, rep_row, n_reps), m, g0, c, lo, hi = self._cut
+        self.groups, self.inv, self.slot = gall[g0:g0 + c], inv[lo:hi], slot[m]
+        self.order, self.offs = order[lo:hi], offs[g0 + m:g0 + m + c + 1]
+        self.kmap, self.rep_row = kmap[m], rep_row[g0 * 9:(g0 + c) * 9]
+        self.n_reps = n_reps[m] if n_reps is not None else None
+        return self.__dict__[name]
+
+
+# The update's plan as native launches (csrc/merlin_plan.hip) for CUDA tensors: WindowPlan.native instead of
+# FrameGroups + WindowPlan + the four SegmentPlans (one radix sort per list, three host reads), and the bulk minibatch
+# builder as one sort, one scan, one pass and one host read instead of the torch chain of epoch_minibatches /
+# _bulk_minibatches.  The torch code stays as the oracle and serves CPU tensors, bulk=False and minibatch().  Same
+# arrays, element for element (tests/test_gpu_native_plan.py).  On by default: 204.65 vs 211.26 ms per bench iteration,
+# medians of three alternated pairs, the parent's spread 0.09 ms (profiles/r16_bench.log); MERLIN_NATIVE_PLAN=0 in the
+# environment turns it off.
+NATIVE_PLAN = os.environ.get("MERLIN_NATIVE_PLAN", "1") != "0"
+_PLAN_WORKSPACE = nat.PlanWorkspace()
+
+
 def _frame_csr(starts: torch.Tensor, n: int) -> torch.Tensor:
     out = torch.empty(starts.numel() + 1, dtype=torch.int32, device=starts.device)
     out[:-1] = starts
@@ -304,14 +338,87 @@ class WindowPlan:
         dk, do = torch.sort(torch.cat(ddst).to(torch.int32), stable=True)
         self.dq_plan = SegmentPlan(dk, torch.cat(dsrc)[do], item_len)
 
+    @classmethod
+    def native(cls, codes: torch.Tensor, item_len: int | None = None, hist_item_len: int | None = None):
+        """(FrameGroups, WindowPlan) of CUDA codes from the native planner (csrc/merlin_plan.hip): what
+        FrameGroups(codes) and WindowPlan(codes, groups, ...) build, array for array (rep: any member of its group),
+        in five stages of one sort each.  The plan is None when the groups are not ok (a hash collision).  Three
+        host reads: a stage's list length is the count of the stage before (frames and windows; patches; bands)."""
+        from . import dedup
+
+        pl = nat.PlanLists(codes, dedup._MULT, _PLAN_WORKSPACE)
+        F, bad, nw = pl.counts.tolist()[:3]
+        fg = dedup.FrameGroups.__new__(dedup.FrameGroups)
+        fg.uid, fg.rep, fg.num_groups, fg.ok = pl.uid, pl.rep[:F], F, not bad
+        if bad:
+            return fg, None
+
+        def L(n, given):
+            return auto_item_len(n) if given is None else int(given)
+
+        def seg(n, item, lst):
+            sp = SegmentPlan.__new__(SegmentPlan)
+            sp.nnz, sp.item_len, sp.nitems = n, item, (n + item - 1) // item
+            sp.key, sp.idx, sp.fix, sp.head_fix = lst
+            sp.counters = torch.zeros(sp.nitems, dtype=torch.int32, device=codes.device)
+            return sp
+
+        plan = cls.__new__(cls)
+        plan.frame_groups, plan.num_frames, plan.num_windows = fg, F, nw
+        Lh = L(16 * nw, hist_item_len)
+        plan.wid, plan.rows, hist = pl.windows(F, nw, Lh)
+        Lp = L(9 * F, item_len)
+        plan.kid, patch = pl.patches(F, Lp)
+        c = pl.counts.tolist()
+        assert not c[3], "a window reads a conv2 table row past LUT2_ROWS"
+        K = plan.num_patches = c[4]
+        Lb = L(3 * K, item_len)
+        band = pl.bands(K, Lb)
+        nb = plan.num_bands = pl.counts.tolist()[5]
+        Ld = L(3 * nb, item_len)
+        dq = pl.dq(nb, nw, Ld)
+        plan.hist, plan.patch_plan = seg(16 * nw, Lh, hist), seg(9 * F, Lp, patch)
+        plan.band_plan, plan.dq_plan = seg(3 * K, Lb, band), seg(3 * nb, Ld, dq)
+        # the planner's device counters; [6] is set when a band's window is not among the frames' windows, which the
+        # construction rules out (not worth a host read of its own: the tests read it)
+        plan.native_counts = pl.counts
+        return fg, plan
+
     def update_minibatches(self, perms: list, minibatch_size: int, bulk: bool = False) -> list:
         """epoch_minibatches for every epoch's permutation at once: one stable sort and one host
         read for the whole update (each host read drains the stream; per epoch that was ten
         pipeline drains per update).  Returns one list of MinibatchWindows per epoch."""
         B = int(perms[0].numel())
-        flat = self.epoch_minibatches(torch.cat(perms), minibatch_size, period=B, bulk=bulk)
         nmb = (B + minibatch_size - 1) // minibatch_size
+        if (bulk and NATIVE_PLAN and perms[0].is_cuda and B * len(perms) < 2 ** 31
+                and nmb * len(perms) * self.num_frames < 2 ** 31):
+            flat = self._native_minibatches(torch.cat(perms), minibatch_size, B)
+        else:
+            flat = self.epoch_minibatches(torch.cat(perms), minibatch_size, period=B, bulk=bulk)
         return [flat[e * nmb:(e + 1) * nmb] for e in range(len(perms))]
+
+    def _native_minibatches(self, idxs: torch.Tensor, minibatch_size: int, P: int) -> list:
+        """_bulk_minibatches' arrays from merlin_plan_minibatches, then the live-patch maps as there; the one host
+        read is the per-minibatch group offsets."""
+        F, K = self.num_frames, self.num_patches
+        uid = self.frame_groups.uid
+        gkey, gall, inv, slot, order, offs, goff = nat.plan_minibatches(idxs.contiguous(), P, minibatch_size,
+                                                                        uid.long().contiguous(), F, _PLAN_WORKSPACE)
+        goff_h = goff.tolist()  # the host read
+        nmb = len(goff_h) - 2
+        if goff_h[nmb + 1]:
+            raise nat.MerlinNativeError("merlin_plan_minibatches: a sample index or a frame id is out of range")
+        G = goff_h[nmb]
+        kmap, rep_row = nat.minibatch_patch_maps(self.kid, gkey[:G], F, goff, nmb, K)
+        n_reps = (kmap >= 0).sum(dim=1) if nat.KernelTimer.active() else None
+        arrays = (gall, inv, slot, order, offs, kmap, rep_row, n_reps)
+        per = (P + minibatch_size - 1) // minibatch_size
+        out = []
+        for m in range(nmb):
+            e, k = divmod(m, per)
+            out.append(_BulkViews(arrays, m, goff_h[m], goff_h[m + 1] - goff_h[m], e * P + k * minibatch_size,
+                                  e * P + min(P, (k + 1) * minibatch_size)))
+        return out
 
     def _bulk_minibatches(self, uniq, inv, perm, starts, mb_of, counts, P, per, minibatch_size) -> list:
         """Every minibatch's MinibatchWindows tensors for the whole update in a few launches (merlin/fast_step.py:
