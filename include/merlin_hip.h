@@ -1058,6 +1058,53 @@ int merlin_level_scores(const float *adv_dev, const int32_t *level_dev, int32_t 
 int merlin_level_scores_host(const float *adv_host, const int32_t *level_host, int32_t T, int32_t N, int64_t L,
                              int32_t kind, int64_t *sum_host, int64_t *count_host, int32_t accumulate);
 
+/* ---- level editing -----------------------------------------------------------------------------------
+ * The edit rule.  A level is `size` = S wall rows, a goal (gx, gy) and an agent (x, y, dir), in merlin_env_snapshot's
+ * layouts.  Child c of generation g is its parent after E edits applied in order e = 0 .. E - 1; edit e draws
+ *   u_j  = the action draw's counter-keyed uniform in (0, 1] of (edit_seed, epoch g, step e, env c, j), j = 0, 1, 2
+ *   kind = min((int)floor(u_0 * 4.0), 3)
+ *   n    = min((int64)floor(u_1 * (double)((S-2)*(S-2))), (S-2)*(S-2) - 1)
+ *   cell = (x, y) = (1 + n % (S-2), 1 + n / (S-2)): always an interior cell, the walled border is never touched
+ *   kind 0, 1: toggle the wall bit at the cell; nothing if the cell is the agent's or the goal's
+ *   kind 2:    the goal moves to the cell; nothing if it is a wall, the agent's cell or the goal's own
+ *   kind 3:    the agent moves to the cell with dir = min((int)floor(u_2 * 4.0), 3); nothing if it is a wall or the
+ *              goal's cell (the agent's own cell is allowed: a turn in place)
+ * One double multiply and a floor per value: a restatement in another language is exact.  Per child the rule gives the
+ * edited map, changed (uint8: 1 iff the walls, goal or agent differ from the parent's -- two toggles of one cell
+ * cancel) and dist (int32: merlin_shortest_paths' value at the child's start pose, -1 if the goal cannot be reached).
+ * A valid parent (border walled, agent and goal on distinct free cells) gives a valid child, possibly an unsolvable
+ * one.
+ *
+ * merlin_levels_mutate: parents walls_dev uint32[P][size], goal_dev int32[P][2], agent_dev int32[P][4]; child c < C
+ * edits parent parent_index_dev[c] (int32[C]; NULL: parent c, and then C <= P) into out_walls_dev uint32[C][size],
+ * out_goal_dev int32[C][2], out_agent_dev int32[C][4], dist_dev int32[C], changed_dev uint8[C].  An index outside
+ * [0, P) reads nothing: that child is all-zero rows, zero goal and agent, dist -1, changed 0.  edits = 0 copies the
+ * parents (changed 0, dist the parents').  size outside 5..32, edits outside 0..64, a negative count or a null pointer
+ * (parent_index_dev aside): MERLIN_E_INVALID; C = 0: nothing to do.  One kernel (csrc/merlin_level_edit.hip), no
+ * allocation, no host sync: capturable. */
+int merlin_levels_mutate(const uint32_t *walls_dev, const int32_t *goal_dev, const int32_t *agent_dev, int64_t P,
+                         const int32_t *parent_index_dev, int64_t C, int32_t size, int32_t edits, uint64_t edit_seed,
+                         uint64_t generation, uint32_t *out_walls_dev, int32_t *out_goal_dev, int32_t *out_agent_dev,
+                         int32_t *dist_dev, uint8_t *changed_dev, void *stream);
+/* [host] the same on host arrays in plain C++ (the search is merlin_shortest_paths_host's). */
+int merlin_levels_mutate_host(const uint32_t *walls_host, const int32_t *goal_host, const int32_t *agent_host, int64_t P,
+                              const int32_t *parent_index_host, int64_t C, int32_t size, int32_t edits,
+                              uint64_t edit_seed, uint64_t generation, uint32_t *out_walls_host, int32_t *out_goal_host,
+                              int32_t *out_agent_host, int32_t *dist_host, uint8_t *changed_host);
+/* Child j < C (walls_dev uint32[C][size], goal_dev int32[C][2], agent_dev int32[C][4]) is packed into slot slot_dev[j]
+ * (int32[C]) of the bound bank as merlin_env_set_levels packs it; a slot outside [0, L) skips its child (a rejected
+ * child is dropped without a host read); distinct valid slots are the caller's to guarantee.  Stream-ordered and in
+ * place: the bank's buffers keep their addresses, so a graph captured earlier plays the new maps without a re-capture.
+ * The CDF, the draw counters and the envs' RNG are not touched.  An env that is inside a replaced slot keeps its own
+ * copy of the old map to the end of its episode and its current level becomes -1: the step's level log writes -1 for
+ * its remaining steps (merlin_level_scores skips them), so no step on the old map is credited to the new level.  No
+ * allocation, no host sync: capturable.  Before merlin_env_set_levels: MERLIN_E_INVALID. */
+int merlin_env_replace_levels(merlin_env *env, const int32_t *slot_dev, const uint32_t *walls_dev,
+                              const int32_t *goal_dev, const int32_t *agent_dev, int64_t C, void *stream);
+/* The bound bank copied out in merlin_env_snapshot's layouts: walls_dev uint32[L][size], goal_dev int32[L][2],
+ * agent_dev int32[L][4], each nullable.  One kernel: capturable.  Before merlin_env_set_levels: MERLIN_E_INVALID. */
+int merlin_env_level_bank(merlin_env *env, uint32_t *walls_dev, int32_t *goal_dev, int32_t *agent_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

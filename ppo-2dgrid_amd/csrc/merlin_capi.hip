@@ -29,6 +29,7 @@ struct merlin_env {
     // that and after a NULL assignment
     uint8_t *diff_buf = nullptr;
     int32_t *level_log = nullptr;  // merlin_env_set_level_log: where the next step launches log the envs' levels
+    uint8_t *lv_flags = nullptr;   // merlin_env_replace_levels' scratch, uint8[lv_n]: the slots a call replaces
     // (level mode, merlin_env_set_levels: dev.lv_* are buffers the context owns from one binding to the next or to the
     // unbinding; a graph captured under a binding reads that binding's buffers)
 };
@@ -572,7 +573,7 @@ int merlin_env_destroy(merlin_env *e) {
     merlin::EnvDev &d = e->dev;
     void *ptrs[] = {d.walls, d.agent, d.rng_s, d.rng_i, d.rng_b, d.ep_ret, d.ep_len, d.err, d.visited,
                     d.pg_walls, d.pg_agent, d.pg_rng_s, d.pg_rng_b, d.pg_valid, d.pg_ring, d.rflag, d.bflag,
-                    e->diff_buf, (void *)d.lv_walls, (void *)d.lv_agent, (void *)d.lv_cdf, d.lv_count, d.lv_cur};
+                    e->diff_buf, e->lv_flags, (void *)d.lv_walls, (void *)d.lv_agent, (void *)d.lv_cdf, d.lv_count, d.lv_cur};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     delete e;
@@ -647,9 +648,10 @@ int merlin_env_set_difficulties(merlin_env *e, const int32_t *diff, int32_t n, v
 
 static void free_levels(merlin_env *e) {
     merlin::EnvDev &d = e->dev;
-    void *ptrs[] = {(void *)d.lv_walls, (void *)d.lv_agent, (void *)d.lv_cdf, d.lv_count, d.lv_cur};
+    void *ptrs[] = {(void *)d.lv_walls, (void *)d.lv_agent, (void *)d.lv_cdf, d.lv_count, d.lv_cur, e->lv_flags};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
+    e->lv_flags = nullptr;
     d.lv_n = 0;
     d.lv_walls = nullptr;
     d.lv_agent = nullptr;
@@ -679,6 +681,7 @@ int merlin_env_set_levels(merlin_env *e, const uint32_t *walls, const int32_t *g
     if (err == hipSuccess) err = hipMalloc((void **)&d.lv_cdf, l * sizeof(double));
     if (err == hipSuccess) err = hipMalloc((void **)&d.lv_count, n * sizeof(uint32_t));
     if (err == hipSuccess) err = hipMalloc((void **)&d.lv_cur, n * sizeof(int32_t));
+    if (err == hipSuccess) err = hipMalloc((void **)&e->lv_flags, l);
     if (err == hipSuccess) {
         d.lv_n = (int)L;
         d.lv_seed = level_seed;
@@ -713,6 +716,59 @@ int merlin_env_set_level_log(merlin_env *e, int32_t *log) {
     if (!e) return fail(MERLIN_E_INVALID, "null env");
     if (log && !e->dev.lv_n) return fail(MERLIN_E_INVALID, "merlin_env_set_level_log before merlin_env_set_levels");
     e->level_log = log;
+    return MERLIN_OK;
+}
+
+int merlin_env_replace_levels(merlin_env *e, const int32_t *slot, const uint32_t *walls, const int32_t *goal,
+                              const int32_t *agent, int64_t C, void *stream) {
+    if (!e) return fail(MERLIN_E_INVALID, "null env");
+    if (!e->dev.lv_n) return fail(MERLIN_E_INVALID, "merlin_env_replace_levels before merlin_env_set_levels");
+    if (C < 0) return fail(MERLIN_E_INVALID, "negative child count");
+    if (C == 0) return MERLIN_OK;
+    if (!slot || !walls || !goal || !agent) return fail(MERLIN_E_INVALID, "null argument");
+    HIP_TRY(merlin::launch_level_replace(e->dev, slot, walls, goal, agent, C, e->lv_flags, (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_env_level_bank(merlin_env *e, uint32_t *walls, int32_t *goal, int32_t *agent, void *stream) {
+    if (!e) return fail(MERLIN_E_INVALID, "null env");
+    if (!e->dev.lv_n) return fail(MERLIN_E_INVALID, "merlin_env_level_bank before merlin_env_set_levels");
+    if (!walls && !goal && !agent) return MERLIN_OK;
+    merlin::EnvDev bank = e->dev;  // the bank holds its maps as the envs hold theirs: merlin_env_snapshot's kernel reads it
+    bank.n = bank.lv_n;
+    bank.walls = const_cast<uint32_t *>(bank.lv_walls);
+    bank.agent = const_cast<uint4 *>(bank.lv_agent);
+    HIP_TRY(merlin::launch_env_snapshot(bank, walls, goal, agent, (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+static int mutate_args(int64_t P, const int32_t *parent, int64_t C, int32_t size, int32_t edits, bool required) {
+    const char *range = (edits < 0 || edits > 64) ? "edits must be in [0, 64]" : P < 0 ? "negative parent count" : nullptr;
+    const int rc = map_args(size, range, C, "negative child count", required);
+    if (rc) return rc;
+    if (!parent && C > P) return fail(MERLIN_E_INVALID, "without a parent index, C <= P");
+    return 0;
+}
+
+int merlin_levels_mutate(const uint32_t *walls, const int32_t *goal, const int32_t *agent, int64_t P,
+                         const int32_t *parent, int64_t C, int32_t size, int32_t edits, uint64_t edit_seed,
+                         uint64_t generation, uint32_t *out_walls, int32_t *out_goal, int32_t *out_agent, int32_t *dist,
+                         uint8_t *changed, void *stream) {
+    ARGS_TRY(mutate_args(P, parent, C, size, edits,
+                         walls && goal && agent && out_walls && out_goal && out_agent && dist && changed));
+    HIP_TRY(merlin::launch_levels_mutate(walls, goal, agent, P, parent, C, size, edits, edit_seed, generation, out_walls,
+                                         out_goal, out_agent, dist, changed, (hipStream_t)stream));
+    return MERLIN_OK;
+}
+
+int merlin_levels_mutate_host(const uint32_t *walls, const int32_t *goal, const int32_t *agent, int64_t P,
+                              const int32_t *parent, int64_t C, int32_t size, int32_t edits, uint64_t edit_seed,
+                              uint64_t generation, uint32_t *out_walls, int32_t *out_goal, int32_t *out_agent,
+                              int32_t *dist, uint8_t *changed) {
+    ARGS_TRY(mutate_args(P, parent, C, size, edits,
+                         walls && goal && agent && out_walls && out_goal && out_agent && dist && changed));
+    merlin::levels_mutate_host(walls, goal, agent, P, parent, C, size, edits, edit_seed, generation, out_walls, out_goal,
+                               out_agent, dist, changed);
     return MERLIN_OK;
 }
 

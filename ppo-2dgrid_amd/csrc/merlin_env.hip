@@ -956,27 +956,61 @@ __global__ __launch_bounds__(256) void k_env_full_obs(EnvDev E, uint8_t *__restr
     p[2] = st;
 }
 
-// merlin_env_set_levels: thread j packs level j of a bank in merlin_env_snapshot's layouts (walls uint32[L][S], goal
-// int32[L][2], agent int32[L][4] = x, y, dir, 0) into the bank the resets read (rows padded to SP, the agent format),
-// coordinates clamped into the grid, and writes the uniform CDF entry (j + 1) / L; thread j < n zeroes env j's draw
-// counter and sets its current level to -1
+// One map in merlin_env_snapshot's layouts (row j of walls uint32[.][S], goal int32[.][2], agent int32[.][4] = x, y, dir,
+// 0) packed into slot l of the bank the resets read: rows padded to SP, the agent format, coordinates clamped into the
+// grid.  merlin_env_set_levels and merlin_env_replace_levels pack with these lines.
+__device__ __forceinline__ void pack_level(const EnvDev &E, size_t l, const uint32_t *__restrict__ walls,
+                                           const int32_t *__restrict__ goal, const int32_t *__restrict__ agent,
+                                           size_t j, uint32_t *__restrict__ lv_walls, uint4 *__restrict__ lv_agent) {
+    const int S = E.size;
+    for (int y = 0; y < E.sp; y++) lv_walls[l * E.sp + y] = y < S ? walls[j * S + y] : 0u;
+    const int ax = min(max(agent[4 * j + 0], 0), S - 1), ay = min(max(agent[4 * j + 1], 0), S - 1);
+    const int gx = min(max(goal[2 * j + 0], 0), S - 1), gy = min(max(goal[2 * j + 1], 0), S - 1);
+    lv_agent[l] = pack_agent(ax, ay, agent[4 * j + 2] & 3, 0, gx, gy, ax, ay, 0);
+}
+
+// merlin_env_set_levels: thread j packs level j of a bank (pack_level) and writes the uniform CDF entry (j + 1) / L;
+// thread j < n zeroes env j's draw counter and sets its current level to -1
 __global__ __launch_bounds__(256) void k_level_bind(EnvDev E, const uint32_t *__restrict__ walls,
                                                     const int32_t *__restrict__ goal, const int32_t *__restrict__ agent,
                                                     uint32_t *__restrict__ lv_walls, uint4 *__restrict__ lv_agent,
                                                     double *__restrict__ lv_cdf) {
     const int j = blockIdx.x * 256 + threadIdx.x;
-    const int S = E.size, L = E.lv_n;
+    const int L = E.lv_n;
     if (j < L) {
-        for (int y = 0; y < E.sp; y++) lv_walls[(size_t)j * E.sp + y] = y < S ? walls[(size_t)j * S + y] : 0u;
-        const int ax = min(max(agent[4 * (size_t)j + 0], 0), S - 1), ay = min(max(agent[4 * (size_t)j + 1], 0), S - 1);
-        const int gx = min(max(goal[2 * (size_t)j + 0], 0), S - 1), gy = min(max(goal[2 * (size_t)j + 1], 0), S - 1);
-        lv_agent[j] = pack_agent(ax, ay, agent[4 * (size_t)j + 2] & 3, 0, gx, gy, ax, ay, 0);
+        pack_level(E, (size_t)j, walls, goal, agent, (size_t)j, lv_walls, lv_agent);
         lv_cdf[j] = (double)(j + 1) / (double)L;
     }
     if (j < E.n) {
         E.lv_count[j] = 0u;
         E.lv_cur[j] = -1;
     }
+}
+
+// merlin_env_replace_levels, first launch: thread j packs child j into slot slot[j] of the bank in place and flags the
+// slot; a slot outside [0, L) skips its child.  Distinct valid slots are the caller's to guarantee.
+__global__ __launch_bounds__(256) void k_level_replace(EnvDev E, const int32_t *__restrict__ slot,
+                                                       const uint32_t *__restrict__ walls,
+                                                       const int32_t *__restrict__ goal,
+                                                       const int32_t *__restrict__ agent, int64_t C,
+                                                       uint32_t *__restrict__ lv_walls, uint4 *__restrict__ lv_agent,
+                                                       uint8_t *__restrict__ flags) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= C) return;
+    const int l = slot[j];
+    if (l < 0 || l >= E.lv_n) return;
+    pack_level(E, (size_t)l, walls, goal, agent, (size_t)j, lv_walls, lv_agent);
+    flags[l] = 1;
+}
+
+// second launch: an env inside a replaced slot plays its own copy of the old map to the end of its episode (take_level
+// copied it), so it is in no level of the bank any more: its current level becomes -1, which the step's level log
+// writes and merlin_level_scores skips.  Its draw counter is untouched: its next map is drawn as before.
+__global__ __launch_bounds__(256) void k_level_retire(EnvDev E, const uint8_t *__restrict__ flags) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= E.n) return;
+    const int l = E.lv_cur[i];
+    if (l >= 0 && l < E.lv_n && flags[l]) E.lv_cur[i] = -1;
 }
 
 __global__ __launch_bounds__(256) void k_env_levels(EnvDev E, int32_t *__restrict__ cur, uint32_t *__restrict__ count) {
@@ -994,6 +1028,18 @@ hipError_t launch_level_bind(const EnvDev &E, const uint32_t *walls, const int32
     hipLaunchKernelGGL(k_level_bind, dim3((m + 255) / 256), dim3(256), 0, s, E, walls, goal, agent,
                        const_cast<uint32_t *>(E.lv_walls), const_cast<uint4 *>(E.lv_agent),
                        const_cast<double *>(E.lv_cdf));
+    return hipGetLastError();
+}
+
+hipError_t launch_level_replace(const EnvDev &E, const int32_t *slot, const uint32_t *walls, const int32_t *goal,
+                                const int32_t *agent, int64_t C, uint8_t *flags, hipStream_t s) {
+    hipError_t e = zero_async(flags, (size_t)E.lv_n, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_level_replace, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, E, slot, walls, goal, agent,
+                       C, const_cast<uint32_t *>(E.lv_walls), const_cast<uint4 *>(E.lv_agent), flags);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_level_retire, dim3((E.n + 255) / 256), dim3(256), 0, s, E, flags);
     return hipGetLastError();
 }
 

@@ -350,6 +350,17 @@ hipError_t launch_env_refill(const EnvDev &E, bool full, hipStream_t s);
 hipError_t launch_level_bind(const EnvDev &E, const uint32_t *walls, const int32_t *goal, const int32_t *agent,
                              hipStream_t s);
 hipError_t launch_env_levels(const EnvDev &E, int32_t *cur, uint32_t *count, hipStream_t s);
+// level editing: children packed into slots of the bound bank in place (merlin_env.hip; flags: the
+// context's uint8[lv_n] scratch), and the editor itself (merlin_level_edit.hip)
+hipError_t launch_level_replace(const EnvDev &E, const int32_t *slot, const uint32_t *walls, const int32_t *goal,
+                                const int32_t *agent, int64_t C, uint8_t *flags, hipStream_t s);
+hipError_t launch_levels_mutate(const uint32_t *walls, const int32_t *goal, const int32_t *agent, int64_t P,
+                                const int32_t *parent, int64_t C, int size, int edits, uint64_t seed,
+                                uint64_t generation, uint32_t *out_walls, int32_t *out_goal, int32_t *out_agent,
+                                int32_t *dist, uint8_t *changed, hipStream_t s);
+void levels_mutate_host(const uint32_t *walls, const int32_t *goal, const int32_t *agent, int64_t P,
+                        const int32_t *parent, int64_t C, int S, int edits, uint64_t seed, uint64_t generation,
+                        uint32_t *out_walls, int32_t *out_goal, int32_t *out_agent, int32_t *dist, uint8_t *changed);
 // per-level scores (merlin_levels.hip)
 hipError_t launch_level_scores(const float *adv, const int32_t *level, int T, int N, int L, int kind, int64_t *sum,
                                int64_t *count, int accumulate, hipStream_t s);

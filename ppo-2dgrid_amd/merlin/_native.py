@@ -223,6 +223,11 @@ def lib():
     L.merlin_level_draw_host.argtypes = [C.c_uint64, i64, i64, i64, i64, vp, i64, vp]
     L.merlin_level_scores.argtypes = [vp, vp, i32, i32, i64, i32, vp, vp, i32, vp]
     L.merlin_level_scores_host.argtypes = [vp, vp, i32, i32, i64, i32, vp, vp, i32]
+    u64 = C.c_uint64
+    L.merlin_levels_mutate.argtypes = [vp, vp, vp, i64, vp, i64, i32, i32, u64, u64, vp, vp, vp, vp, vp, vp]
+    L.merlin_levels_mutate_host.argtypes = [vp, vp, vp, i64, vp, i64, i32, i32, u64, u64, vp, vp, vp, vp, vp]
+    L.merlin_env_replace_levels.argtypes = [vp, vp, vp, vp, vp, i64, vp]
+    L.merlin_env_level_bank.argtypes = [vp, vp, vp, vp, vp]
     check_env_config_layout(L)
     _lib = L
     return L
@@ -283,6 +288,7 @@ EXPORTED_SYMBOLS = (
     "merlin_env_set_levels", "merlin_env_set_level_cdf", "merlin_env_levels", "merlin_env_set_level_log",
     "merlin_level_draw_host",
     "merlin_level_scores", "merlin_level_scores_host",
+    "merlin_levels_mutate", "merlin_levels_mutate_host", "merlin_env_replace_levels", "merlin_env_level_bank",
     "merlin_plan_minibatches_workspace", "merlin_plan_minibatches", "merlin_plan_sort_workspace",
     "merlin_plan_frames", "merlin_plan_windows", "merlin_plan_patches", "merlin_plan_bands", "merlin_plan_dq",
 )
@@ -2235,3 +2241,56 @@ def level_scores_host(adv, levels, L: int, kind="l1_value", sum=None, count=None
                                          np_ptr(sum), np_ptr(count), int(bool(accumulate))),
           "merlin_level_scores_host")
     return sum, count
+
+
+# ---- level editing (merlin/level_edit.py) ------------------------------------------------------------
+MAX_LEVEL_EDITS = 64
+
+
+def levels_mutate(walls: torch.Tensor, goal: torch.Tensor, agent: torch.Tensor, parent_index, size: int, edits: int,
+                  seed: int, generation: int, count: int | None = None, out=None):
+    """(walls int32[C, size], goal int32[C, 2], agent int32[C, 4], dist int32[C], changed uint8[C]) on the device: child
+    c is parent parent_index[c] (int32[C]; None: parent c, C = `count` or P) after `edits` edits of the rule in
+    include/merlin_hip.h, keyed (seed, generation, edit, c) (merlin_levels_mutate: one kernel, no host sync).  An
+    index outside [0, P) gives a zero child with dist -1, changed 0.  `out`: the five tensors to write."""
+    S, P = int(size), int(walls.shape[0])
+    assert walls.dtype == torch.int32 and walls.dim() == 2 and walls.shape[1] == S
+    assert goal.dtype == torch.int32 and goal.shape == (P, 2) and agent.dtype == torch.int32 and agent.shape == (P, 4)
+    if parent_index is not None:
+        assert parent_index.dtype == torch.int32 and parent_index.dim() == 1
+        Cn = int(parent_index.numel())
+    else:
+        Cn = P if count is None else int(count)
+    dev = walls.device
+    if out is None:
+        out = (torch.empty((Cn, S), dtype=torch.int32, device=dev), torch.empty((Cn, 2), dtype=torch.int32, device=dev),
+               torch.empty((Cn, 4), dtype=torch.int32, device=dev), torch.empty((Cn,), dtype=torch.int32, device=dev),
+               torch.empty((Cn,), dtype=torch.uint8, device=dev))
+    ow, og, oa, dist, changed = out
+    assert ow.dtype == og.dtype == oa.dtype == dist.dtype == torch.int32 and changed.dtype == torch.uint8
+    assert ow.numel() == Cn * S and og.numel() == Cn * 2 and oa.numel() == Cn * 4
+    assert dist.numel() == Cn and changed.numel() == Cn
+    with torch.cuda.device(dev), KernelTimer.span("k_levels_mutate", Cn * (2 * S * 4 + 53)):
+        check(lib().merlin_levels_mutate(ptr(walls), ptr(goal), ptr(agent), P, ptr(parent_index), Cn, S, int(edits),
+                                         int(seed) & 0xFFFFFFFFFFFFFFFF, int(generation) & 0xFFFFFFFFFFFFFFFF,
+                                         ptr(ow), ptr(og), ptr(oa), ptr(dist), ptr(changed), stream_of(walls)),
+              "merlin_levels_mutate")
+    return out
+
+
+def levels_mutate_host(walls, goal, agent, parent_index, size: int, edits: int, seed: int, generation: int,
+                       count: int | None = None):
+    """levels_mutate on numpy arrays, in plain C++ on the CPU (merlin_levels_mutate_host): (walls uint32[C, size], goal
+    int32[C, 2], agent int32[C, 4], dist int32[C], changed uint8[C])."""
+    import numpy as np
+
+    S, P, walls, goal, agent = _host_maps(size, walls, goal, (agent, "int32", (4,)))
+    pi = None if parent_index is None else np.ascontiguousarray(np.asarray(parent_index, dtype=np.int32)).reshape(-1)
+    Cn = int(pi.size) if pi is not None else (P if count is None else int(count))
+    n = max(Cn, 0)
+    out = (np.zeros((n, S), dtype=np.uint32), np.zeros((n, 2), dtype=np.int32), np.zeros((n, 4), dtype=np.int32),
+           np.zeros((n,), dtype=np.int32), np.zeros((n,), dtype=np.uint8))
+    check(lib().merlin_levels_mutate_host(np_ptr(walls), np_ptr(goal), np_ptr(agent), P, np_ptr(pi), Cn, S, int(edits),
+                                          int(seed) & 0xFFFFFFFFFFFFFFFF, int(generation) & 0xFFFFFFFFFFFFFFFF,
+                                          *(np_ptr(a) for a in out)), "merlin_levels_mutate_host")
+    return out

@@ -336,6 +336,37 @@ class MerlinVecEnv:
             assert log.dtype == torch.int32 and log.is_contiguous() and log.numel() % self.num_envs == 0
         nat.check(self._lib.merlin_env_set_level_log(self._h, nat.ptr(log)), "merlin_env_set_level_log")
 
+    # -- level editing (merlin/level_edit.py) --------------------
+    def replace_levels(self, slots: torch.Tensor, children) -> None:
+        """Child j of `children` (a LevelSet, or (walls int32[C, size], goal int32[C, 2], agent int32[C, 4])) is packed
+        into slot slots[j] (int32[C]) of the bound bank, in place and stream-ordered; a slot outside [0, num_levels)
+        skips its child; distinct valid slots are the caller's to guarantee.  The bank keeps its addresses: step launches
+        captured into a graph play the new maps without a re-capture.  The CDF and the draw counters are untouched.  An
+        env inside a replaced slot plays its copy of the old map to the end of its episode; its current level becomes
+        -1, and so do the entries of the level log for its remaining steps (merlin_env_replace_levels: no host sync).
+        The env's own `level_set` mirror is not touched: LevelSet.replace_ updates it."""
+        walls, goal, agent = ((children.walls, children.goal, children.agent) if hasattr(children, "walls")
+                              else children)
+        Cn = int(slots.numel())
+        assert slots.dtype == torch.int32 and walls.dtype == goal.dtype == agent.dtype == torch.int32
+        assert tuple(walls.shape) == (Cn, self.size) and tuple(goal.shape) == (Cn, 2) and tuple(agent.shape) == (Cn, 4)
+        with torch.cuda.device(self.device):
+            nat.check(self._lib.merlin_env_replace_levels(self._h, nat.ptr(slots), nat.ptr(walls), nat.ptr(goal),
+                                                          nat.ptr(agent), Cn, self._stream),
+                      "merlin_env_replace_levels")
+
+    def level_bank(self):
+        """(walls int32[L, size], goal int32[L, 2], agent int32[L, 4]): the bound bank as the resets read it, copied out
+        in snapshot()'s layouts (merlin_env_level_bank: one kernel, capturable)."""
+        L = max(self.num_levels, 1)
+        walls = torch.empty((L, self.size), dtype=torch.int32, device=self.device)
+        goal = torch.empty((L, 2), dtype=torch.int32, device=self.device)
+        agent = torch.empty((L, 4), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            nat.check(self._lib.merlin_env_level_bank(self._h, nat.ptr(walls), nat.ptr(goal), nat.ptr(agent),
+                                                      self._stream), "merlin_env_level_bank")
+        return walls, goal, agent
+
     def set_refill_interval(self, every: int) -> None:
         """Refill the used look-ahead map slots every `every` step calls (default 16); 0 leaves the
         refills to the caller's refill() (merlin_env_set_refill_interval)."""

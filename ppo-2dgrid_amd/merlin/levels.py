@@ -19,11 +19,18 @@ from . import _native as nat
 
 class LevelSet:
     """walls int32[L, size] bit rows (bit x of row y = wall at (x, y)), goal int32[L, 2], agent int32[L, 4] = (x, y,
-    dir, 0): torch tensors on one device.  ``seeds`` / ``difficulties``: what the levels were built from, or None."""
+    dir, 0): torch tensors on one device.  ``seeds`` / ``difficulties``: what the levels were built from, or None.
+    Lineage (level editing, merlin/level_edit.py): ``generation`` int32[L], 0 for a seed-built, hand-made or loaded level,
+    else the editing round that made it; ``parent`` int32[L], the slot its parent held in that round, -1 for none."""
 
     def __init__(self, walls: torch.Tensor, goal: torch.Tensor, agent: torch.Tensor, size: int, seeds=None,
-                 difficulties=None):
+                 difficulties=None, generation=None, parent=None):
         self.walls, self.goal, self.agent = walls, goal, agent
+        n = int(walls.shape[0])
+        self.generation = (torch.zeros(n, dtype=torch.int32, device=walls.device) if generation is None
+                           else generation.to(device=walls.device, dtype=torch.int32))
+        self.parent = (torch.full((n,), -1, dtype=torch.int32, device=walls.device) if parent is None
+                       else parent.to(device=walls.device, dtype=torch.int32))
         self.size = int(size)
         self.seeds = None if seeds is None else [int(s) for s in seeds]
         self.difficulties = None if difficulties is None else [str(d) for d in difficulties]
@@ -32,6 +39,8 @@ class LevelSet:
             raise ValueError(f"a level set holds 1..{nat.MAX_LEVELS} levels, got {L}")
         if tuple(walls.shape) != (L, self.size) or tuple(goal.shape) != (L, 2) or tuple(agent.shape) != (L, 4):
             raise ValueError("LevelSet: walls [L, size], goal [L, 2], agent [L, 4]")
+        if tuple(self.generation.shape) != (L,) or tuple(self.parent.shape) != (L,):
+            raise ValueError("LevelSet: generation [L], parent [L]")
 
     def __len__(self) -> int:
         return int(self.walls.shape[0])
@@ -45,7 +54,22 @@ class LevelSet:
         if dev == self.device:
             return self
         return LevelSet(self.walls.to(dev), self.goal.to(dev), self.agent.to(dev), self.size, self.seeds,
-                        self.difficulties)
+                        self.difficulties, self.generation.to(dev), self.parent.to(dev))
+
+    def replace_(self, slots: torch.Tensor, children: "LevelSet", generation, parent: torch.Tensor) -> None:
+        """Child j of `children` takes slot slots[j] in place, with lineage (generation: one int or int32[C]; parent
+        int32[C]); a slot < 0 drops its child.  A masked scatter into the existing tensors, no host sync: every holder of
+        this set (the trainer, the env's mirror, an evaluation) sees the new levels.  Distinct slots >= 0 are the
+        caller's to guarantee."""
+        L = len(self)
+        slots = slots.to(torch.int64)
+        idx = torch.where(slots >= 0, slots, torch.full_like(slots, L))  # a dropped child lands in a spare row
+        gen = torch.as_tensor(generation, dtype=torch.int32, device=slots.device).expand(slots.shape)
+        for dst, src in ((self.walls, children.walls), (self.goal, children.goal), (self.agent, children.agent),
+                         (self.generation, gen), (self.parent, parent)):
+            tmp = torch.cat([dst, dst[:1]])
+            tmp[idx] = src.to(dst.dtype)
+            dst.copy_(tmp[:L])
 
     @classmethod
     def from_seeds(cls, seeds, difficulty="mediumhard", difficulties=None, size: int = 16, device="cuda") -> "LevelSet":
@@ -125,7 +149,8 @@ class LevelSet:
         if self.difficulties is not None:
             extra["difficulties"] = np.asarray(self.difficulties)
         np.savez(path, walls=self.walls.cpu().numpy(), goal=self.goal.cpu().numpy(), agent=self.agent.cpu().numpy(),
-                 size=np.int32(self.size), **extra)
+                 size=np.int32(self.size), generation=self.generation.cpu().numpy(), parent=self.parent.cpu().numpy(),
+                 **extra)
 
     @classmethod
     def load(cls, path: str, device=None) -> "LevelSet":
@@ -138,6 +163,12 @@ class LevelSet:
                 ls.seeds = [int(s) for s in z["seeds"]]
             if "difficulties" in z.files:
                 ls.difficulties = [str(d) for d in z["difficulties"]]
+            for name in ("generation", "parent"):  # lineage: files written before level editing have none
+                if name in z.files:
+                    v = np.asarray(z[name])
+                    if v.shape != (len(ls),) or not np.issubdtype(v.dtype, np.integer):
+                        raise ValueError(f"{path}: {name} is int[{len(ls)}]")
+                    getattr(ls, name).copy_(torch.from_numpy(v.astype(np.int32)))
         return ls
 
 
@@ -153,7 +184,9 @@ class LevelSampler:
                                    level was seen this iteration); P_seen = (1 - rho) P_S + rho P_C.  The seen levels
                                    share |seen| / L as P_seen, the unseen ones share the rest uniformly (1 / L each):
                                    the proportionate replay schedule.
-    No host sync in either."""
+    forget(slots)                  the slots >= 0 become unseen (score 0, last_seen 0): a level that was replaced.  An
+                                   unseen level has weight 1 / L under the proportionate schedule.
+    No host sync in any."""
 
     def __init__(self, L: int, strategy: str = "uniform", beta: float = 0.1, rho: float = 0.1,
                  score: str = "l1_value", device="cuda"):
@@ -179,6 +212,15 @@ class LevelSampler:
         self.last_seen = torch.where(now, torch.full_like(self.last_seen, int(iteration)), self.last_seen)
         self.seen = self.seen | now
         self.iteration = int(iteration)
+
+    def forget(self, slots: torch.Tensor) -> None:
+        slots = slots.to(torch.int64)
+        hit = torch.zeros(self.L + 1, dtype=torch.bool, device=self.score.device)
+        hit[torch.where(slots >= 0, slots, torch.full_like(slots, self.L))] = True  # -1 lands in the spare entry
+        hit = hit[:self.L]
+        self.score = torch.where(hit, torch.zeros_like(self.score), self.score)
+        self.last_seen = torch.where(hit, torch.zeros_like(self.last_seen), self.last_seen)
+        self.seen = self.seen & ~hit
 
     def weights(self) -> torch.Tensor:
         """float64[L]: the probability of each level (sums to 1 up to rounding)."""

@@ -51,6 +51,13 @@ def optimal_paths(seeds, difficulty="mediumhard", size: int = 16, device="cuda",
     return dist.cpu().tolist(), optimal_reward(dist, ms).cpu().tolist()
 
 
+def level_optimal_steps(level_set) -> torch.Tensor:
+    """int32[L] on the set's device: dist of every level of a merlin.levels.LevelSet from its start pose, one launch."""
+    from . import _native as nat
+
+    return nat.shortest_paths(level_set.walls, level_set.goal, level_set.agent, level_set.size)
+
+
 def oracle_actions(field: torch.Tensor, walls: torch.Tensor, goal: torch.Tensor, agent: torch.Tensor) -> torch.Tensor:
     """int64[n]: an action on a shortest path for each pose agent[q] = (x, y, dir, 0) of map q -- field int16[n, 4, S,
     S] (MerlinVecEnv.distance_field), walls int32[n, S], goal int32[n, 2] (snapshot()), all on one device.  Forward

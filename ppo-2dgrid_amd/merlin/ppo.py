@@ -92,7 +92,7 @@ class PPO:
                  batch_size=2048, minibatch_size=256, vf_coef=0.5, ent_coef=0.01, device="cuda",
                  *, dp: DataParallel | None = None, perm_fn=None, conv1_from_codes: bool = True,
                  dedup: bool = True, windows: bool = True, rollout_graph: bool = True, level_set=None,
-                 level_sampler=None, level_seed: int = 0):
+                 level_sampler=None, level_seed: int = 0, level_editor=None):
         self.env = env
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -211,6 +211,11 @@ class PPO:
                 raise ValueError(f"a sampler over {self.level_sampler.L} levels for a set of {len(level_set)}")
         elif level_sampler is not None:
             raise ValueError("level_sampler without level_set")
+        # level editing (merlin/level_edit.py): a round of mutation inside _update_levels, between the sampler's update
+        # and the CDF it hands to the env
+        self.level_editor = level_editor
+        if level_editor is not None and (self.level_set is None or self.level_sampler.strategy != "plr"):
+            raise ValueError("level_editor needs a level_set and a 'plr' level_sampler")
         # every parameter a view of one flat buffer (merlin/fast_step.py: the weight stage reads it with one
         # indexed gather; done before anything captures parameter addresses)
         from .fast_step import flatten_parameters
@@ -539,7 +544,10 @@ class PPO:
     def _update_levels(self):
         """Score the levels of the last rollout from its un-normalised advantages (merlin_level_scores), sum the
         integer vectors across ranks -- every rank then builds the same CDF -- update the sampler and hand its CDF to
-        the env: the next rollout's resets (the captured graph's included) draw from it."""
+        the env: the next rollout's resets (the captured graph's included) draw from it.  With a level editor, a round
+        of mutation runs on the updated scores first: its children replace bank slots in place and enter the CDF as
+        unseen levels (the edit key holds no rank and the scores are the all-reduced ones: every rank builds the same
+        bank)."""
         buf, sampler = self.buf, self.level_sampler
         L = len(self.level_set)
         s, c = nat.level_scores(buf.adv, buf.levels, L, sampler.score_kind)
@@ -547,6 +555,8 @@ class PPO:
         self.dp.allreduce_sum_(c)
         self.level_iteration += 1
         sampler.update(s, c, self.level_iteration)
+        if self.level_editor is not None and self.level_editor.due(self.level_iteration):
+            self.level_editor.evolve(self.level_set, sampler, self.vec, self.level_iteration)
         cdf = sampler.cdf()
         self.vec.set_level_cdf(cdf)
         self.last_level_scores, self.last_level_cdf = (s, c), cdf

@@ -22,6 +22,14 @@ Same flags and defaults as the reference, plus:
                     l1_value|positive_value).  Each iteration logs levels/train_* (every training level from its start
                     pose), levels/test_* (--eval_episodes held-out seeds 200000 + i) and their gap, levels/seen,
                     levels/score_mean and the sampling weights' histogram.  Needs --num_envs > 1.
+  --level_replay accel   prioritized level replay plus level editing (ACCEL, merlin/level_edit.py): every
+                    --accel_every K-th update (default 1) the --accel_children C highest-scoring levels (default
+                    num_levels / 8, at least 1) each get a child by --accel_edits E random edits (default 4: toggle a
+                    wall, move the goal, move the agent); a child that changed and whose optimal path takes at least
+                    --accel_min_dist D actions (default 1: solvable) replaces a level the sampler weighs least, in place
+                    under the captured rollout.  Logs levels/children_accepted, levels/generation_mean,
+                    levels/edited_share (levels with generation > 0) and levels/optimal_steps_mean.
+  --save_levels PATH   write the final bank with its lineage (merlin.levels.LevelSet.save: generation, parent).
 Outputs keep the reference's layout: checkpoints/<env_id>_<WxH>_<difficulty>_<ts>/seed_<s>/
 {best_model, ppo_model_<k>k, ppo_model_final}.pth (CNNActorCritic state_dicts with the
 reference's keys) and tb_logs/... scalars (TensorBoard when installed, else scalars.jsonl).
@@ -86,7 +94,12 @@ def parse_args(argv=None):
     p.add_argument("--num_levels", type=int, default=0, help="train on the levels of seeds B .. B + K - 1")
     p.add_argument("--level_seed_base", type=int, default=0)
     p.add_argument("--level_file", type=str, default=None, help="a saved merlin.levels.LevelSet (.npz)")
-    p.add_argument("--level_replay", type=str, default="uniform", choices=["uniform", "plr"])
+    p.add_argument("--level_replay", type=str, default="uniform", choices=["uniform", "plr", "accel"])
+    p.add_argument("--accel_children", type=int, default=None, help="children per editing round (default: L / 8)")
+    p.add_argument("--accel_edits", type=int, default=4)
+    p.add_argument("--accel_min_dist", type=int, default=1)
+    p.add_argument("--accel_every", type=int, default=1)
+    p.add_argument("--save_levels", type=str, default=None, help="write the final level bank (.npz) with lineage")
     p.add_argument("--plr_beta", type=float, default=0.1)
     p.add_argument("--plr_rho", type=float, default=0.1)
     p.add_argument("--plr_score", type=str, default="l1_value", choices=["l1_value", "positive_value"])
@@ -171,7 +184,9 @@ def train_minigrid(args):
         # rank r's single env is global env r: seed + r, and its action draws are keyed by r
         env = sc.create_env(args.difficulty, seed=args.seed, device=device, env_offset=rank, **size_kw, **flags)
         env.vec.set_base_seed(args.seed)  # create_env ignores its seed, like the reference's
-    level_set = level_sampler = None
+    level_set = level_sampler = level_editor = None
+    if (args.level_replay == "accel" or args.save_levels) and not (args.num_levels or args.level_file):
+        raise SystemExit("--level_replay accel / --save_levels need a level set: --num_levels or --level_file")
     if args.num_levels or args.level_file:
         from merlin.levels import LevelSampler, LevelSet
         from merlin.task_mix import parse_mix
@@ -189,12 +204,20 @@ def train_minigrid(args):
             level_set = LevelSet.from_seeds(
                 range(args.level_seed_base, args.level_seed_base + args.num_levels), size=env.size, device=device,
                 difficulties=[classes[i % len(classes)] for i in range(args.num_levels)])
-        level_sampler = LevelSampler(len(level_set), args.level_replay, beta=args.plr_beta, rho=args.plr_rho,
-                                     score=args.plr_score, device=device)
+        accel = args.level_replay == "accel"
+        level_sampler = LevelSampler(len(level_set), "plr" if accel else args.level_replay, beta=args.plr_beta,
+                                     rho=args.plr_rho, score=args.plr_score, device=device)
+        if accel:
+            from merlin.level_edit import LevelEditor
+
+            level_editor = LevelEditor(args.accel_children or max(1, len(level_set) // 8), edits=args.accel_edits,
+                                       min_dist=args.accel_min_dist, every=args.accel_every, seed=args.seed)
     agent = PPO(env, lr=args.lr, gamma=args.gamma, lam=args.lam, clip_eps=args.clip_eps,
                 update_epochs=args.update_epochs, batch_size=batch, minibatch_size=args.minibatch_size,
                 vf_coef=args.vf_coef, ent_coef=args.ent_coef, device=device, dp=dp, level_set=level_set,
-                level_sampler=level_sampler, level_seed=args.seed)
+                level_sampler=level_sampler, level_seed=args.seed, level_editor=level_editor)
+    if level_set is not None:
+        level_set = agent.level_set  # the bank the trainer holds: an editor evolves it in place
 
     env_id = sc.get_env_id(args.difficulty)
     size = args.size or int(sc.get_env_size_str(args.difficulty).split("x")[0])
@@ -258,6 +281,17 @@ def train_minigrid(args):
                            ("levels/return_gap", tr_m - te_m), ("levels/seen", seen),
                            ("levels/score_mean", float(sm.score[sm.seen].mean().item()) if seen else 0.0)):
                 writer.add_scalar(tag, v, step_count)
+            if level_editor is not None:
+                from merlin.pathing import level_optimal_steps
+
+                gen = level_set.generation
+                for tag, v in (("levels/children_accepted", float(level_editor.last_accepted.item())
+                                if level_editor.last_accepted is not None else 0.0),
+                               ("levels/generation_mean", float(gen.double().mean().item())),
+                               ("levels/edited_share", float((gen > 0).double().mean().item())),
+                               ("levels/optimal_steps_mean",
+                                float(level_optimal_steps(level_set).double().mean().item()))):
+                    writer.add_scalar(tag, v, step_count)
             writer.add_histogram("levels/sampling_weights", sm.weights().cpu().numpy(), step_count)
             print(f"[{step_count:>7}] levels | train {tr_s:.3f} / R {tr_m:.3f} | test {te_s:.3f} / R {te_m:.3f} | "
                   f"gap {tr_s - te_s:+.3f} | seen {seen}/{len(level_set)}", flush=True)
@@ -291,6 +325,8 @@ def train_minigrid(args):
     if lead:
         torch.save(agent.ac.state_dict(), os.path.join(ckpt_subdir, "ppo_model_final.pth"))
         writer.close()
+        if args.save_levels:
+            agent.level_set.save(args.save_levels)
     return agent
 
 
