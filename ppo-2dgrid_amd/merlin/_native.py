@@ -296,6 +296,7 @@ EXPORTED_SYMBOLS = (
 
 _CAPTURE_DEPTH = 0
 _DEFERRED: list = []
+_BOUND: list = []  # one list per open capture_guard: the module-level buffers its capture was handed
 
 _hip_rt = None
 _cu_streams = []  # raw handles of the CU-masked streams (kept for the process's lifetime)
@@ -335,21 +336,35 @@ def capture_guard():
     from earlier agents: a MerlinVecEnv's merlin_env_destroy (hipFree) or an old torch.cuda.CUDAGraph destroyed
     mid-capture invalidates it or aborts the process (gpurun_out/t_w.log, round 3).  So: collect first, keep
     the collector off until the capture ends, and have native handles released while a capture is open
-    (merlin.envs.MerlinVecEnv.close) queue their release until it has ended."""
+    (merlin.envs.MerlinVecEnv.close) queue their release until it has ended.
+    Yields the list of this module's own buffers that launches inside the capture were handed (bind_to_capture): the
+    graph recorded their addresses, so whoever keeps the graph keeps that list for as long as the graph can replay."""
     global _CAPTURE_DEPTH
     drain_deferred()
     gc.collect()
     was_enabled = gc.isenabled()
     gc.disable()
     _CAPTURE_DEPTH += 1
+    bound: list = []
+    _BOUND.append(bound)
     try:
-        yield
+        yield bound
     finally:
+        _BOUND.pop()
         _CAPTURE_DEPTH -= 1
         if _CAPTURE_DEPTH == 0:
             if was_enabled:
                 gc.enable()
             run_deferred()
+
+
+def bind_to_capture(t: torch.Tensor) -> torch.Tensor:
+    """A module-level buffer on its way to a kernel.  Inside a capture_guard the capture records its address, and the
+    module may replace the buffer later (a scratch that grows with the shape): the open capture's list takes a
+    reference, so the buffer stays allocated where it is for as long as the list is kept."""
+    if _BOUND and not any(t is b for b in _BOUND[-1]):
+        _BOUND[-1].append(t)
+    return t
 
 
 def capturing() -> bool:
@@ -991,7 +1006,11 @@ _SLABS = {}
 
 def conv2_lut_bwd_grouped(codes, dZ2c, absmax):
     """Grouped conv2_lut_bwd: dtables f32 [2G, 2720, 64] from chunk-major dZ2c f32 [2G, 16, F*25, 4]
-    (F = frames per group) of frames codes [G * F, 8] (group g's rows contiguous)."""
+    (F = frames per group) of frames codes [G * F, 8] (group g's rows contiguous).
+    The histogram's slabs (pure scratch: written whole, then folded, by every call) are one buffer per device that a
+    call needing more replaces; a capture that recorded the old one keeps it through bind_to_capture.  A call that
+    needs more while its stream is capturing takes a buffer of its own from the graph's pool and leaves the module's
+    alone: memory of a graph's pool is not handed to later eager calls."""
     T = int(dZ2c.shape[0])
     F = int(dZ2c.shape[2]) // 25
     assert codes.dtype == torch.int32 and codes.shape == ((T // 2) * F, OBS_WORDS) and codes.is_contiguous()
@@ -999,7 +1018,10 @@ def conv2_lut_bwd_grouped(codes, dZ2c, absmax):
     key = dZ2c.device
     slabs = _SLABS.get(key)
     if slabs is None or slabs.numel() < nbytes:
-        slabs = _SLABS[key] = torch.empty(nbytes, dtype=torch.uint8, device=dZ2c.device)
+        slabs = torch.empty(nbytes, dtype=torch.uint8, device=dZ2c.device)
+        if not torch.cuda.is_current_stream_capturing():
+            _SLABS[key] = slabs
+    bind_to_capture(slabs)
     dt = torch.empty((T, LUT2_ROWS, 64), dtype=torch.float32, device=dZ2c.device)
     with KernelTimer.span("k_conv2_lut_hist", F * (T * 25 * 64 * 4 + 16 * T * 32)):
         check(lib().merlin_tower_conv2_lut_bwd_grouped(ptr(codes), F, ptr(dZ2c), ptr(absmax), T, ptr(dt), ptr(slabs),

@@ -56,6 +56,7 @@ class FewShotAdapter:
     def close(self):
         if self.fm._env is not None:
             self.fm._rollouts.clear()
+            self.fm._kept.clear()
             self.fm._env.close()
             self.fm._env = None
 

@@ -63,6 +63,9 @@ class FOMAML:
         self._env = None
         self._task_seeds = None
         self._rollouts = {}  # per rollout kind: storage, weight pack and its captured HIP graph
+        # per (kind, tasks, steps): the storage of every shape a kind has had (_rollout_state).  Never trimmed, like
+        # _steps whose graphs read it: one storage + weight pack (~6 MB per task) per shape seen, for the object's life
+        self._kept = {}
         self.rollout_graph = True
         # the acting step as merlin_group_act + merlin_env_act_step (two library launches + the draw fused into the
         # env step) instead of grouped_policy.act_packed (~15 torch / library launches) + merlin_env_step; the draws
@@ -95,12 +98,20 @@ class FOMAML:
     def _rollout_state(self, key, G, steps, params):
         st = self._rollouts.get(key)
         per_env = bool(self._env is not None and self._env.per_env_classes)
-        if st is not None and st["G"] == G and st["steps"] == steps:
+        if st is not None and (st["G"], st["steps"]) != (G, steps):
+            # another shape under this key.  The captured inner / outer graphs of the old shape (self._steps) read
+            # its storage by address, so the storage is kept, never reallocated, and serves that shape again when
+            # it comes back: a captured graph is only ever replayed with the tensors it bound
+            self._kept[(key, st["G"], st["steps"])] = st
+            st = self._kept.get((key, G, steps))
+            if st is not None:
+                self._rollouts[key] = st
+        if st is not None:
             if st["per_env"] != per_env:  # recorded before the env read its class buffer: record again, same storage
                 st["graph"], st["per_env"] = None, per_env
             return st
         dev = self.device
-        st = {"G": G, "steps": steps, "graph": None, "per_env": per_env,
+        st = {"G": G, "steps": steps, "graph": None, "env": None, "per_env": per_env,
               "codes": torch.zeros((steps + 1, G, 8), dtype=torch.int32, device=dev),
               "act": torch.zeros((steps, G), dtype=torch.int64, device=dev),
               "logp": torch.zeros((steps, G), dtype=torch.float32, device=dev),
@@ -156,6 +167,8 @@ class FOMAML:
             W = 1 if self.fused_act else G  # (merlin_group_act shared_weights; the torch path needs G copies)
             params = {n: p.detach().unsqueeze(0).expand(W, *p.shape) for n, p in self.meta_policy.named_parameters()}
         st = self._rollout_state(key, G, steps, params)
+        if st["graph"] is not None and st["env"] is not env:
+            st["graph"] = None  # recorded on an env that has been replaced since: record again, same storage
         if st["graph"] is None:
             gp.pack_into(st["pack"], params)
             self._rollout_body(env, st)
@@ -163,9 +176,10 @@ class FOMAML:
                 torch.cuda.synchronize(self.device)
                 g = torch.cuda.CUDAGraph()
                 try:
-                    with nat.capture_guard(), torch.cuda.graph(g):  # no GC finalisers inside the capture
+                    with nat.capture_guard() as bound, torch.cuda.graph(g):  # no GC finalisers inside the capture
                         self._rollout_body(env, st)
-                    st["graph"] = g
+                    # bound: as in _phase (no module-level buffer is on the acting path today)
+                    st["graph"], st["env"], st["bound"] = g, env, bound
                 except Exception:  # keep launching eagerly
                     self.rollout_graph = False
                     torch.cuda.synchronize(self.device)
@@ -259,13 +273,15 @@ class FOMAML:
         torch.cuda.synchronize(self.device)
         g = torch.cuda.CUDAGraph()
         try:
-            with nat.capture_guard(), torch.cuda.graph(g):
+            with nat.capture_guard() as bound, torch.cuda.graph(g):
                 out = fn(*args)
         except Exception:  # an op this stack cannot capture: keep launching eagerly
             self.capture_steps = False
             torch.cuda.synchronize(self.device)
             return fn(*args)
-        st[name], st[name + "_out"] = g, out
+        # bound: the library's module-level scratch the graph recorded by address (merlin._native.bind_to_capture),
+        # kept alive next to the graph -- the module replaces its own buffer when a later call needs a larger one
+        st[name], st[name + "_out"], st[name + "_bound"] = g, out, bound
         g.replay()  # the capture recorded the launches without running them
         return out
 
